@@ -21,7 +21,7 @@ all ranks' evaluations / the slowest rank's time.  CASIM_BENCH_SCALING=strong sp
 same 100 groups over the N GPUs instead (rank 0 drives them through
 ca_multi_estimate_plan_run, or CASIM_BENCH_MULTI=rccl: one block per rank).
 
-At N > 1 the line also carries the configs that name several GPUs, every rank running one
+At N > 1 a --full run's line also carries the configs that name several GPUs, every rank running one
 contiguous block of units on its own mirror replica (one process per GPU, RCCL all-gathers
 over xGMI): extra.c3_multi (BASELINE configs[2]: the C3 sweep's candidates, the blocks'
 lastIndex chain composed in the phases of casim.h "one process per GPU"), extra.c4_multi
@@ -29,7 +29,15 @@ lastIndex chain composed in the phases of casim.h "one process per GPU"), extra.
 one C5 RunOnce, Estimate and the sweep sharded), each with results_identical_to_1gpu, the
 collective bytes and the CPU port's time.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+A plain run does what the headline needs and no more: set-up, W warm-up steps, the K timed
+steps, the result line (metric, value, ms_per_step, config; roofline and cpu_baseline null).
+--dump-outputs DIR also writes what the last timed step returned to DIR/<name>.npy (the
+inputs are seeded: the same arguments give the same files on every run and every build).
+--full adds, after the headline, everything else this file measures: the per-phase times and
+the roofline record, extra.device_resident / host_int32_ids / cold, the CPU baseline, the
+other legs (each with its --no-* switch) and, at N > 1, the multi-GPU configs below.
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
        (--gpus N > 1 without WORLD_SIZE starts N ranks under torch.distributed.run itself;
        with WORLD_SIZE set it must equal N.  Fewer GPUs than ranks: the ranks share devices
        and use gloo — a rehearsal, said so in config.devices)
@@ -75,6 +83,12 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run everything else: phase times and roofline, the device-resident "
+                         "and 32-bit-id variants, cold latency, the CPU baseline and the other legs (see --no-*)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (Estimate's per-group results, the scheduled pods, "
+                         "lastIndex) as DIR/<name>.npy, float64")
     ap.add_argument("--pods", type=int, default=50_000)
     ap.add_argument("--groups", type=int, default=100)
     ap.add_argument("--existing", type=int, default=1000)
@@ -93,7 +107,10 @@ def parse():
     ap.add_argument("--no-runonce", action="store_true", help="skip the C5 end-to-end RunOnce leg (N=1)")
     ap.add_argument("--no-planner", action="store_true", help="skip the planner (canPersist=true) leg (N=1)")
     ap.add_argument("--sweep-nodes", type=int, default=5000)
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def cpu_model() -> str:
@@ -105,6 +122,38 @@ def cpu_model() -> str:
     except OSError:
         pass
     return platform.processor() or "unknown"
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path: str, out, group_off) -> None:
+    """--dump-outputs: what the last timed step handed its caller, as float64 .npy files under
+    `path`: one array per field of Estimate's per-group results (results_<field>, [groups]),
+    sched_pod (the scheduled pods in placement order, CSR by group_off; 16-bit podset
+    indices and 32-bit pod ids are the same numbers) and last_index.  Entries of sched_pod
+    past a group's n_scheduled are not part of the result and are written as -1.  Arrays
+    that together exceed 64 MB are cut to a fixed, seeded sample of their entries."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {}
+    if out is not None:
+        for f in out.results.dtype.names:
+            arrays[f"results_{f}"] = out.results[f].astype(np.float64)
+        if out.sched_pod is not None:
+            sp = out.sched_pod
+            sp = np.where(sp == 0xFFFF, -1, sp.astype(np.int64)) if sp.dtype == np.uint16 else sp.astype(np.int64)
+            off = np.asarray(group_off, np.int64)
+            pos = np.arange(len(sp), dtype=np.int64) - np.repeat(off[:-1], np.diff(off))
+            sp[pos >= np.repeat(out.results["n_scheduled"].astype(np.int64), np.diff(off))] = -1
+            arrays["sched_pod"] = sp.astype(np.float64)
+        arrays["last_index"] = np.array([out.last_index], np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    rng = np.random.default_rng(0)
+    for name, a in arrays.items():
+        if total > DUMP_LIMIT_BYTES and a.nbytes > 1 << 20:      # (small arrays stay whole: half the limit is theirs)
+            keep = int(a.size * (DUMP_LIMIT_BYTES / 2) / total)
+            a = a[np.sort(rng.choice(a.size, keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def c4_leg(args, device: int, with_cpu: bool) -> dict:
@@ -868,13 +917,17 @@ def multi_main(args, world: int, rank: int, dist, coll_dev: str):
         st = plan.stats()
         pods = out.sched_pod.copy()
         res = out.results.copy()
-        # the same batch on one device: identical outputs (the multi path's parity)
-        with native.EstimatePlan(mirrors[0], w.table, w.group_off, w.pod_idx, w.templates) as one:
-            o1 = one.run(w.max_nodes, 0, want_nodes=False)
-        same = bool(np.array_equal(o1.results, res) and np.array_equal(o1.sched_pod, pods)
-                    and o1.last_index == out.last_index)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, out, w.group_off)
+        same = None
+        if args.full:
+            # the same batch on one device: identical outputs (the multi path's parity)
+            with native.EstimatePlan(mirrors[0], w.table, w.group_off, w.pod_idx, w.templates) as one:
+                o1 = one.run(w.max_nodes, 0, want_nodes=False)
+            same = bool(np.array_equal(o1.results, res) and np.array_equal(o1.sched_pod, pods)
+                        and o1.last_index == out.last_index)
         cpu = None
-        if not args.no_cpu_baseline and world == 1:              # (rank 0 at N = 1 only)
+        if args.full and not args.no_cpu_baseline and world == 1:              # (rank 0 at N = 1 only)
             sys.path.insert(0, os.path.join(ROOT, "oracle"))
             import pyoracle                                       # CPU baseline leg only
             o = pyoracle.OracleState()
@@ -1077,6 +1130,60 @@ def main():
     host_pods = hout.sched_pod.copy() if hout is not None else None
     if host_pods is not None and host_pods.dtype == np.uint16:
         host_pods = np.where(host_pods == 0xFFFF, -1, host_pods.astype(np.int32))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, hout, off_blk)
+    ms = elapsed / args.steps * 1e3
+    result = {
+        "metric": METRIC,
+        "value": total_evals / elapsed,
+        "unit": "evals/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms,
+        "higher_is_better": True,
+        "scaling": scaling,
+        "vs_baseline": None,
+        "dtype": "int64",
+        "data": "synthetic: seeded C2 generator (autoscaler_amd/workloads.py), 64-shape pod catalog",
+        "config": {
+            "workload": "C2: heterogeneous pending pods x node-group templates, resource-fit only "
+                        "(BASELINE.json configs[1]); one step = Estimate() for every group, every group's "
+                        "node count and scheduled pods on the host",
+            "pods": args.pods, "groups": n_groups_total, "groups_per_gpu": g1 - g0,
+            "existing_nodes": args.existing,
+            "max_nodes_per_scaleup": args.max_nodes,
+            "parallelism": (f"{n_groups_total} groups = {args.groups} per GPU x {world} GPU(s) (weak scaling), "
+                            if scaling == "weak" else f"the {args.groups} groups in {world} contiguous blocks, ")
+                           + "one block per GPU (one process each), lastIndex chained by an all_gather of a "
+                             "4-int record per rank per step",
+        },
+        "roofline": None,
+        "cpu_baseline": None,
+        "extra": {
+            "estimate_latency_ms": ms,
+            "items_per_s": items * args.steps / elapsed,
+            "evals_per_step": total_evals / args.steps,
+            "rank0_groups": [g0, g1],
+        },
+    }
+    if shared:
+        result["config"]["devices"] = f"{world} ranks sharing {torch.cuda.device_count()} GPU(s): a rehearsal " \
+                                      "of the N-GPU launch (gloo collectives), not an N-GPU measurement"
+
+    def finish():
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        plan.close()
+        mirror.close()
+        return result if rank == 0 else None
+
+    if not args.full:
+        return finish()           # a plain run: the headline alone; everything below is --full's
+
     # per-phase device times: the same steps again, untimed
     chain_ms, sort_ms, rounds, phases, pub = [], [], [], [], []
     plan.set_phase_timing(True)
@@ -1160,7 +1267,6 @@ def main():
         if not args.no_runonce:
             multi_legs["c5_runonce_multi"] = c5_multi_leg(args, ctx)
 
-    result = None
     if rank == 0:
         cpu = None
         if not args.no_cpu_baseline and world == 1:              # (rank 0 at N = 1 only)
@@ -1178,69 +1284,39 @@ def main():
                    "sample": f"oracle/casim_oracle.c Estimate of {g} of the {args.groups} C2 groups (one batch, "
                              f"{cpu_evals} evals in {cpu_s:.2f} s) on 1 thread of {cpu_model()}",
                    "estimate_ms": cpu_s * 1e3}
-        ms = elapsed / args.steps * 1e3
-        result = {
-            "metric": METRIC,
-            "value": total_evals / elapsed,
-            "unit": "evals/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": ms,
-            "higher_is_better": True,
-            "scaling": scaling,
-            "vs_baseline": None,
-            "dtype": "int64",
-            "data": "synthetic: seeded C2 generator (autoscaler_amd/workloads.py), 64-shape pod catalog",
-            "config": {
-                "workload": "C2: heterogeneous pending pods x node-group templates, resource-fit only "
-                            "(BASELINE.json configs[1]); one step = Estimate() for every group, every group's "
-                            "node count and scheduled pods on the host",
-                "pods": args.pods, "groups": n_groups_total, "groups_per_gpu": g1 - g0,
-                "existing_nodes": args.existing,
-                "max_nodes_per_scaleup": args.max_nodes,
-                "parallelism": (f"{n_groups_total} groups = {args.groups} per GPU x {world} GPU(s) (weak scaling), "
-                                if scaling == "weak" else f"the {args.groups} groups in {world} contiguous blocks, ")
-                               + "one block per GPU (one process each), lastIndex chained by an all_gather of a "
-                                 "4-int record per rank per step",
-            },
-            "roofline": {
-                "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                "traffic_unit": "HBM bytes per step of the phase (all its launches)",
-                "traffic_source": traffic_src,
-                "kernel": PHASE_KERNEL[dom], "kernel_ms": kernel_ms,
-                "bytes_per_unit": per_item, "unit_of_work": "(pod, node group) item",
-                "units_per_launch": items_blk,
-            },
-            "cpu_baseline": cpu,
-            "extra": {
-                "estimate_latency_ms": ms,
-                "results_to_host": "zero-copy publisher kernel on a second stream writes each final chunk of 4096 "
-                                   "scheduled pods into the caller's page-locked buffer while the chains run, as "
-                                   + ("16-bit podset indices (ca_estimate_plan_run_u16, "
-                                      if host_mode == "u16" else "32-bit pod ids (ca_estimate_plan_run, ")
-                                   + f"{(2 if host_mode == 'u16' else 4) * items} B per step); results path per step: "
-                                   f"{sorted(set(pub)) if pub else None}",
-                "device_resident": device_resident,
-                "host_int32_ids": host_i32,
-                "cold": cold,
-                "sort_ms": float(np.mean(sort_ms)) if sort_ms else None,
-                "phases_ms": ph_mean,
-                "chain_kernel_ms": ph_mean.get("chain_ms"),
-                "items_per_s": items * args.steps / elapsed,
-                "eval_equivalent_GBps": (BYTES_PER_EVAL * (evals / args.steps) / (ph_mean["chain_ms"] / 1e3) / 1e9
-                                         if ph_mean.get("chain_ms") else None),
-                "speculation_rounds": float(np.mean(rounds)) if rounds else None,
-                "evals_per_step": total_evals / args.steps,
-                "rank0_groups": [g0, g1],
-                "speedup_vs_cpu_baseline": (total_evals / elapsed) / cpu["value"] if cpu else None,
-            },
+        result["roofline"] = {
+            "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+            "traffic_unit": "HBM bytes per step of the phase (all its launches)",
+            "traffic_source": traffic_src,
+            "kernel": PHASE_KERNEL[dom], "kernel_ms": kernel_ms,
+            "bytes_per_unit": per_item, "unit_of_work": "(pod, node group) item",
+            "units_per_launch": items_blk,
+        }
+        result["cpu_baseline"] = cpu
+        result["extra"] = {
+            "estimate_latency_ms": ms,
+            "results_to_host": "zero-copy publisher kernel on a second stream writes each final chunk of 4096 "
+                               "scheduled pods into the caller's page-locked buffer while the chains run, as "
+                               + ("16-bit podset indices (ca_estimate_plan_run_u16, "
+                                  if host_mode == "u16" else "32-bit pod ids (ca_estimate_plan_run, ")
+                               + f"{(2 if host_mode == 'u16' else 4) * items} B per step); results path per step: "
+                               f"{sorted(set(pub)) if pub else None}",
+            "device_resident": device_resident,
+            "host_int32_ids": host_i32,
+            "cold": cold,
+            "sort_ms": float(np.mean(sort_ms)) if sort_ms else None,
+            "phases_ms": ph_mean,
+            "chain_kernel_ms": ph_mean.get("chain_ms"),
+            "items_per_s": items * args.steps / elapsed,
+            "eval_equivalent_GBps": (BYTES_PER_EVAL * (evals / args.steps) / (ph_mean["chain_ms"] / 1e3) / 1e9
+                                     if ph_mean.get("chain_ms") else None),
+            "speculation_rounds": float(np.mean(rounds)) if rounds else None,
+            "evals_per_step": total_evals / args.steps,
+            "rank0_groups": [g0, g1],
+            "speedup_vs_cpu_baseline": (total_evals / elapsed) / cpu["value"] if cpu else None,
         }
         result["extra"].update(multi_legs)
-        if shared:
-            result["config"]["devices"] = f"{world} ranks sharing {torch.cuda.device_count()} GPU(s): a rehearsal " \
-                                          "of the N-GPU launch (gloo collectives), not an N-GPU measurement"
         if world == 1 and not args.no_sweep:
             result["extra"]["sweep"] = sweep_leg(args, local, not args.no_cpu_baseline)
         if world == 1 and not args.no_c4:
@@ -1257,13 +1333,7 @@ def main():
             result["extra"]["c5_runonce"] = runonce_leg(args, local, not args.no_cpu_baseline)
         if world == 1 and not args.no_planner:
             result["extra"]["planner"] = planner_leg(args, local, not args.no_cpu_baseline)
-        print(json.dumps(result), flush=True)
-    if dist is not None:
-        dist.barrier()
-        dist.destroy_process_group()
-    plan.close()
-    mirror.close()
-    return result
+    return finish()
 
 
 if __name__ == "__main__":

@@ -1,4 +1,4 @@
-"""One-screen summary of a bench.py JSON line (python scripts/bench_summary.py FILE)."""
+"""One-screen summary of a `bench.py --full` JSON line (python scripts/bench_summary.py FILE)."""
 import json
 import sys
 

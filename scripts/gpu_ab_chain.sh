@@ -4,7 +4,7 @@
 set -o pipefail
 cd "${GRAFT_REPO_ROOT:-$(pwd)}"
 mkdir -p gpurun_out
-H="--no-cpu-baseline --no-sweep --no-c4 --no-expansion --no-util --no-filter --no-unlimited --no-runonce --no-planner"
+H="--full --no-cpu-baseline --no-sweep --no-c4 --no-expansion --no-util --no-filter --no-unlimited --no-runonce --no-planner"
 for v in cw1; do
   if [ $v = base ]; then L=$PWD/autoscaler_amd/lib/libcasim.so; else L=$PWD/autoscaler_amd/lib/$v/libcasim.so; fi
   CASIM_LIB_PATH=$L timeout -k 10 200 python -u bench.py --steps 20 --warmup 3 $H > gpurun_out/ab_$v.json 2>gpurun_out/ab_$v.err || { tail gpurun_out/ab_$v.err; exit 1; }

@@ -6,7 +6,7 @@ mkdir -p gpurun_out
 timeout -k 10 400 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread -k "estimate or gosort or multi or plan or publisher" > gpurun_out/pytest_est.log 2>&1; rc=$?
 tail -2 gpurun_out/pytest_est.log
 [ $rc -eq 0 ] || { tail -40 gpurun_out/pytest_est.log; exit $rc; }
-H="--no-cpu-baseline --no-sweep --no-c4 --no-expansion --no-util --no-filter --no-unlimited --no-runonce --no-planner"
+H="--full --no-cpu-baseline --no-sweep --no-c4 --no-expansion --no-util --no-filter --no-unlimited --no-runonce --no-planner"
 for rep in 1 2 3; do
   timeout -k 10 200 python -u bench.py --steps 40 --warmup 3 $H > gpurun_out/bench_head.json 2> gpurun_out/bench_head.err || { tail gpurun_out/bench_head.err; exit 1; }
   python3 -c "

@@ -3,7 +3,7 @@
 set -o pipefail
 cd "${GRAFT_REPO_ROOT:-$(pwd)}"
 mkdir -p gpurun_out
-ALL="--no-sweep --no-c4 --no-unlimited --no-expansion --no-util --no-filter --no-runonce"
+ALL="--full --no-sweep --no-c4 --no-unlimited --no-expansion --no-util --no-filter --no-runonce"
 for keep in runonce filter sweep; do
   F=$(echo $ALL | sed "s/--no-$keep//")
   timeout -k 10 400 python -u bench.py --steps 5 --warmup 2 --no-cpu-baseline $F > gpurun_out/bench_bis.json 2> gpurun_out/bench_bis.err || { tail gpurun_out/bench_bis.err; exit 1; }

@@ -1,4 +1,4 @@
-"""One-screen summary of a bench.py JSON line (the legs' GPU / CPU-port times and ratios)."""
+"""One-screen summary of a `bench.py --full` JSON line (the legs' GPU / CPU-port times and ratios)."""
 import json
 import sys
 
