@@ -14,12 +14,15 @@
 //   st  (heavy groups)   k_run_table     class ranks + per-class counts of each group's
 //                                        list, each rank's first stream position, the
 //                                        class's stream record against the template.
-//                        k_emit_runs     run heads and the stream windows that hold them.
 //                        k_ffd_chain     one 4-wave workgroup per group: the sequential
 //                                        First-Fit-Decreasing loop (per pod, or per run of
 //                                        identical pods in closed form) with the new-node
-//                                        rows in LDS; pushes 4096-output tickets.
-//   st2 (light groups)   the same three kernels for the groups outside the heavy set.
+//                                        rows in LDS, walking the group's run table (copied
+//                                        to LDS in its prologue); pushes 16384-output tickets.
+//                                        (CASIM_TABLE_CHAIN=0, or a table too large for LDS:
+//                                        k_emit_runs writes run heads and stream windows
+//                                        first and the chain reads those.)
+//   st2 (light groups)   the same kernels for the groups outside the heavy set.
 //   pub_stream           k_publish       claims tickets in completion order and writes the
 //                                        scheduled pods (Go-order ids) into the caller's
 //                                        page-locked buffer while the chains run.
@@ -1607,7 +1610,16 @@ __global__ void __launch_bounds__(256) k_publish(const GroupMeta* __restrict__ g
 // every placed stream position (-1 = not scheduled).
 // PS: the batch has pods with host ports or extended-resource requests (their columns and
 // checks compile out of the common instantiation)
-template <bool GROWS, bool PS>
+// TB: the run-table chain (decoupled stream from per-class counts, run batching on).  The
+// stable order is the group's classes in rank order and every pod of a class is the same
+// record, so k_run_table's rows rstart[g][0..U] / rsp[g][0..U) are the whole stream: the
+// prologue copies them to LDS (at byte tab_off of the dynamic LDS, behind the rows) and
+// lists the ranks that start a run — present ranks, adjacent batchable ranks of equal
+// record merged under k_emit_runs' SF_HEAD rule — and the loop walks that list: a run's
+// record, first position and end come from LDS, `stream` and `heads` are never read and
+// the loop issues no global load (k_emit_runs is not launched).  A non-batchable rank is a
+// run of `count` single pods of one record.
+template <bool GROWS, bool PS, bool TB>
 __global__ void __launch_bounds__(CT) k_ffd_chain(
     const GroupMeta* __restrict__ groups, const StreamPod* __restrict__ stream, const uint64_t* __restrict__ heads,
     const ca_template* __restrict__ tmpls, const ca_pod_spec* __restrict__ specs, const PodHot* __restrict__ ph,
@@ -1617,13 +1629,18 @@ __global__ void __launch_bounds__(CT) k_ffd_chain(
     int64_t* __restrict__ tickets, int32_t* __restrict__ qctl, int32_t nsub, int2* __restrict__ prog, int32_t pch,
     ChainOut* __restrict__ outs, const int32_t* __restrict__ gmap, unsigned char* __restrict__ gslab,
     const int64_t* __restrict__ slab_off, const int32_t* __restrict__ gkcap, int32_t pos_out,
-    ChainOut* __restrict__ hout, int32_t* __restrict__ hflags) {
+    ChainOut* __restrict__ hout, int32_t* __restrict__ hflags, const int32_t* __restrict__ rstart,
+    const StreamPod* __restrict__ rsp, int32_t U, int32_t tab_off) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int g = GSEL(blockIdx.x);
     // GROWS: the group's rows live in its own HBM slab (kcap = the group's pod count, for an
     // unlimited estimate too large for LDS); else in LDS with the batch-wide kcap
     if (GROWS) kcap = gkcap[g];
     unsigned char* const row_base = GROWS ? gslab + slab_off[g] : smem_raw;
+    // TB: the group's rank starts, requested first so they arrive with the group's record
+    const int32_t* const t_rs = TB ? rstart + (size_t)g * (U + 1) : nullptr;
+    int32_t t_a0 = 0, t_b0 = 0;
+    if (TB && (int32_t)threadIdx.x < U) { t_a0 = t_rs[threadIdx.x]; t_b0 = t_rs[threadIdx.x + 1]; }
     if (!need[g]) return;
     if (tickets && threadIdx.x == 0)              // a publisher may wait on this batch now
         __hip_atomic_store(&qctl[4], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1689,8 +1706,10 @@ __global__ void __launch_bounds__(CT) k_ffd_chain(
     // stored when the window moves on, so no step waits on a store (vmcnt counts both).
     int32_t wbase = 0;
     StreamPod cur = {}, nxt = {};
-    if (lane < P) cur = gs[lane];
-    if (64 + lane < P) nxt = gs[64 + lane];
+    if (!TB) {
+        if (lane < P) cur = gs[lane];
+        if (64 + lane < P) nxt = gs[64 + lane];
+    }
     int32_t out_node = -1, out_idx = 0;
     bool pend = false;
     bool stop = false;
@@ -1701,6 +1720,50 @@ __global__ void __launch_bounds__(CT) k_ffd_chain(
     StreamPod pf_cur = {}, pf_nxt = {};
     uint64_t pf_hw = 0;
     const int32_t nhc = (P + 63) >> 6;
+    // TB: the group's table in LDS — TREC[r] the record of rank r (present ranks only),
+    // TST[r] its first position (TST[U] = P), TRUN[i] = (the rank that starts run i, its
+    // first position); TRUN[n_runs] = (0, P): a run ends where the next one starts.  The
+    // loop keeps the next run's record (t_nrec) and the entry after it (t_npair: the next
+    // run's end, the rank of the run after) in registers, read from LDS when the run before
+    // started, so taking a run waits for nothing.
+    StreamPod* const TREC = reinterpret_cast<StreamPod*>(smem_raw + tab_off);
+    int2* const TRUN = reinterpret_cast<int2*>(TREC + (TB ? U : 0));
+    int32_t* const TST = reinterpret_cast<int32_t*>(TRUN + (TB ? U + 1 : 0));
+    int32_t t_next = 0, t_end = 0, n_runs = 0;     // the next run of the list; the current run's end
+    StreamPod t_nrec = {};
+    int2 t_npair = make_int2(0, 0);
+    if (TB) {
+        const StreamPod* rp = rsp + (size_t)g * U;
+        for (int32_t r = tid; r < U; r += CT) {
+            // (the first CT ranks' starts were requested at the kernel's entry)
+            const int32_t a = r < CT ? t_a0 : t_rs[r], b = r < CT ? t_b0 : t_rs[r + 1];
+            TST[r] = a;
+            if (b > a) TREC[r] = rp[r];        // (an absent rank's record was never written)
+        }
+        if (tid == 0) TST[U] = P;
+        cbar<GROWS>();
+        for (int32_t b = 0; b < U; b += CT) {
+            const int32_t r = b + tid;
+            bool head = r < U && TST[r + 1] > TST[r];
+            if (head) {
+                int32_t q = r - 1;             // the present rank before r
+                while (q >= 0 && TST[q + 1] == TST[q]) q--;
+                if (q >= 0) {
+                    const StreamPod x = TREC[q], y = TREC[r];
+                    head = !((x.flags & y.flags & SF_BATCH) && (x.flags & ~SF_BATCH) == (y.flags & ~SF_BATCH) &&
+                             x.cpu == y.cpu && x.mem == y.mem && x.eph == y.eph);
+                }
+            }
+            int32_t tot;
+            const int32_t slot = blk_compact<GROWS>(cred, par, wv, head, tot);
+            if (head) TRUN[n_runs + slot] = make_int2(r, TST[r]);
+            n_runs += tot;
+        }
+        if (tid == 0) TRUN[n_runs] = make_int2(0, P);
+        cbar<GROWS>();
+        t_nrec = TREC[TRUN[0].x];
+        t_npair = TRUN[min(1, n_runs)];
+    }
 
     // add a template copy as new node k (addNewNodeToSnapshot, :146-159)
     // (LDS writes by one thread; a barrier follows before any wave reads the row)
@@ -1736,7 +1799,7 @@ __global__ void __launch_bounds__(CT) k_ffd_chain(
         const int32_t c1 = nsched / pch;
         tk_bound = (c1 + 1) * pch;
         if (pend) {                       // the pending single placement, stored now
-            so_pod[out_idx] = pos_out ? wbase + lane : cur.pod;
+            so_pod[out_idx] = (TB || pos_out) ? wbase + lane : cur.pod;
             pend = false;
         }
         push_chunks(g, tk_next, c1, nsub, tickets, qctl, prog, nseg, nsched, lane, pch, pure_from, pure_off);
@@ -1751,11 +1814,13 @@ __global__ void __launch_bounds__(CT) k_ffd_chain(
         PROF_T(t_top);
         if (pos >= wbase + 64) {
             if (pend) {
-                so_pod[out_idx] = pos_out ? wbase + lane : cur.pod;
+                so_pod[out_idx] = (TB || pos_out) ? wbase + lane : cur.pod;
                 if (so_node) so_node[out_idx] = out_node;
             }
             pend = false;
-            if (pos < wbase + 128) {
+            if (TB) {
+                wbase = pos & ~63;          // (the window only names the lanes of pending placements)
+            } else if (pos < wbase + 128) {
                 cur = nxt;
                 wbase += 64;
                 nxt = StreamPod{};
@@ -1774,9 +1839,18 @@ __global__ void __launch_bounds__(CT) k_ffd_chain(
             pf_base = -1;
         }
         const int sl = pos - wbase;
-        const int64_t pcpu = rl64(cur.cpu, sl), pmem = rl64(cur.mem, sl), peph = rl64(cur.eph, sl);
-        const int32_t pidx = rl32(cur.pod, sl);
-        const uint32_t sf = (uint32_t)rl32((int32_t)cur.flags, sl);
+        if (TB && pos >= t_end) {           // the next run of the table: its record and end
+            cur = t_nrec;                   // (every lane: the same record)
+            cur.flags |= SF_HEAD;           // a batchable run is entered at its head only
+            t_end = rl32(t_npair.y, 0);
+            t_next++;
+            t_nrec = TREC[t_npair.x];       // the run after: in flight behind this run's LDS work
+            t_npair = TRUN[min(t_next + 1, n_runs)];
+        }
+        const int rsl = TB ? 0 : sl;
+        const int64_t pcpu = rl64(cur.cpu, rsl), pmem = rl64(cur.mem, rsl), peph = rl64(cur.eph, rsl);
+        const int32_t pidx = rl32(cur.pod, rsl);
+        const uint32_t sf = (uint32_t)rl32((int32_t)cur.flags, rsl);
         const bool zero = (sf & SF_ZERO) != 0;
 #ifdef CASIM_PROF
         __builtin_amdgcn_s_waitcnt(0);       // (profiling: the head's loads land here, not in the run)
@@ -1787,8 +1861,8 @@ __global__ void __launch_bounds__(CT) k_ffd_chain(
         if (batch_runs && (sf & (SF_BATCH | SF_HEAD)) == (SF_BATCH | SF_HEAD)) {
             PROF_T(t_re);
             PROF_T(t_run);
-            const int32_t e = run_end_pf(hm, pos, P, lane, pf_hc, pf_hw);
-            if (e < P) {
+            const int32_t e = TB ? t_end : run_end_pf(hm, pos, P, lane, pf_hc, pf_hw);
+            if (!TB && e < P) {
                 const int32_t pb = e & ~63;
                 if (pb >= wbase + 128) {
                     pf_base = pb;
@@ -2351,7 +2425,7 @@ __global__ void __launch_bounds__(CT) k_ffd_chain(
     }
     PROF_T(t_epi);
     if (pend) {
-        so_pod[out_idx] = pos_out ? wbase + lane : cur.pod;
+        so_pod[out_idx] = (TB || pos_out) ? wbase + lane : cur.pod;
         if (so_node) so_node[out_idx] = out_node;
     }
     // newNodesWithPods
@@ -2508,6 +2582,7 @@ struct ca_estimate_plan {
     // then needs no k_round_init; false at first and after a publisher gave up)
     bool pub_clean = false;
     int32_t ran_decoupled = 0;     // last run took the decoupled Go order
+    int32_t ran_table_chain = 0;   // ... and its chains walked the run table (k_ffd_chain<.., TB>)
     bool phase_events = true;      // record the per-phase timing events (ca_estimate_plan_set_phase_timing)
     std::vector<uint64_t> diag;     // per group: chain ticks (100 MHz) | single-pod steps << 32
     std::vector<uint8_t> grp_succ;  // last run, per group: a FitsAnyNode call succeeded (moved lastIndex)
@@ -2919,26 +2994,38 @@ int launch_pdq_sort(ca_estimate_plan* p, hipStream_t ss, const int32_t* gm, int3
     return CA_OK;
 }
 
-int32_t pub_blocks(bool decoupled) {
+int32_t pub_blocks(bool decoupled, bool table_chain) {
     const char* e = knob_env("CASIM_PUB_BLOCKS");
     // scripts/pub_sweep.sh on C2: stable order 32 x 4096-output chunks; decoupled Go order
     // 128 x 8192 in round 4 (each group's ids are ready when its own sort ends, from ~0.17 ms
     // on; more blocks in flight keep a block waiting on a late group from holding up the
     // ready ones — 0.474 against 0.478 ms for 64 x 16384, interleaved repeats,
     // scripts/gpu_pubsweep2.sh); with round 6's chains and sort, 64 x 16384 (A/Bs of variant
-    // builds: profiles/r06_pub_chunk_ab.txt, r06_pub_blocks_ab.txt)
+    // builds: profiles/r06_pub_chunk_ab.txt, r06_pub_blocks_ab.txt); with the run-table chain
+    // the publisher's tail behind the sort ends the step, not the chains: 128 blocks
+    // (profiles/table_chain_ab.txt: 0.4396 against 0.4423 ms for 64, 0.4411 for 256)
 #ifndef CASIM_PUB_BLOCKS_DECOUPLED
 #define CASIM_PUB_BLOCKS_DECOUPLED 64
 #endif
-    return e ? std::max(1, atoi(e)) : (decoupled ? CASIM_PUB_BLOCKS_DECOUPLED : 32);
+    return e ? std::max(1, atoi(e)) : (table_chain ? 128 : decoupled ? CASIM_PUB_BLOCKS_DECOUPLED : 32);
 }
 
-size_t chain_lds_bytes(int32_t kcap, bool use_ports, bool use_scalar) {
+// The run-table chain's table of a podset with U score classes (k_ffd_chain<.., TB>): a
+// 32-B record and a first position per rank, and the list of (rank, first position) of
+// the ranks that start a run.
+size_t chain_table_bytes(int32_t U) {
+    return (sizeof(StreamPod) * (size_t)U + (sizeof(int2) + sizeof(int32_t)) * ((size_t)U + 1) + 15) & ~(size_t)15;
+}
+// table_ranks >= 0: with the run table of that many classes behind the rows (which start
+// 16-byte aligned: the table's offset is the size without it)
+size_t chain_lds_bytes(int32_t kcap, bool use_ports, bool use_scalar, int32_t table_ranks = -1) {
     const size_t nb = (size_t)((kcap + 63) >> 6);
     size_t b = 32 * ((size_t)kcap + nb) + 8 * (size_t)kcap;   // rows, summaries, CAPA + ALIVE
     if (use_ports) b += 8 * CA_PORT_WORDS * (size_t)kcap;
     if (use_scalar) b += 8 * CA_MAX_SCALAR * (size_t)kcap;
-    return (b + 15) & ~(size_t)15;
+    b = (b + 15) & ~(size_t)15;
+    if (table_ranks >= 0) b += chain_table_bytes(table_ranks);
+    return b;
 }
 
 int plan_run(ca_estimate_plan* p, const ca_limiter* lim, int32_t* last_index, ca_estimate_result* results,
@@ -3036,9 +3123,10 @@ int plan_run(ca_estimate_plan* p, const ca_limiter* lim, int32_t* last_index, ca
     // ranks, k_pdq_sort, ids into d_spod_go and per-group ready flags holding this run's
     // epoch (no reset between runs; every run is synchronised before it returns).  The
     // chains meanwhile run on the stable class order (same class at every position).  It
-    // is queued right after the heavy chains when the groups split (the heavy chains are the
-    // step's critical path; the sort only bounds when the publisher can start and ends well
-    // before them), else before anything else.
+    // is queued right after the heavy chains when the groups split and the chains read the
+    // emitted stream (the heavy chains are then the step's critical path; the sort only
+    // bounds when the publisher can start and ends well before them), else before anything
+    // else (sort_first, below).
     // (the run's epoch is set before anything is queued: every consumer launched below reads it)
     if (decoupled) {
         if (p->ids_epoch == INT32_MAX) {                  // (wrapped: start over from a clean table)
@@ -3086,6 +3174,23 @@ int plan_run(ca_estimate_plan* p, const ca_limiter* lim, int32_t* last_index, ca
     // the chains
     const bool fast_init = decoupled && runs_stream && (!publish || p->pub_clean) && !serial_pub && !serial_pub_r1 &&
                            !knob_env("CASIM_NO_FAST_INIT");
+    // The run-table chain (k_ffd_chain<.., TB>): the chains read the run table itself, so
+    // k_emit_runs is not launched and d_stream / d_heads are not read; the table of round 1
+    // serves the later speculation rounds.  Bound: the table — 44 B per score class of the
+    // podset + 12 B (chain_table_bytes) — must fit the CU's 160 KB of LDS beside the rows
+    // (or alone, with the rows in HBM slabs) and the reduction scratch; a podset with more
+    // classes than that keeps the stream.  CASIM_TABLE_CHAIN=0: the stream path (tests, A/B).
+    size_t tab_off = 0;
+    bool table_chain = decoupled && runs_stream && batch_runs && p->bucket &&
+                       !(knob_env("CASIM_TABLE_CHAIN") && atoi(knob_env("CASIM_TABLE_CHAIN")) == 0);
+    if (table_chain) {
+        tab_off = grows ? 0 : lds;
+        const size_t with_table = grows ? chain_table_bytes(p->s->n_cls)
+                                        : chain_lds_bytes(kcap, p->use_ports, p->use_scalar, p->s->n_cls);
+        if (with_table + sizeof(ChainRed) > 160 * 1024) { table_chain = false; tab_off = 0; }
+        else lds = with_table;
+    }
+    p->ran_table_chain = table_chain ? 1 : 0;
     const int32_t lin0 = *last_index;
     if (publish) p->pub_clean = false;        // set again once this run's publishers all finished clean
     bool pub_gave_up = false;
@@ -3145,7 +3250,14 @@ int plan_run(ca_estimate_plan* p, const ca_limiter* lim, int32_t* last_index, ca
         gmapB = gmapA + p->n_heavy;
     }
     const int32_t nA = split ? p->n_heavy : G, nB = split ? G - p->n_heavy : 0;
-    const bool sort_after_heavy = split && p->total > 0 && p->bucket && !knob_env("CASIM_SORT_FIRST");
+    // With the run-table chain the heavy chains end ~60 us before the publisher does (C2:
+    // profiles/table_chain_timeline.txt): the step's end is the Go-order sort's end plus the
+    // ~110 us the publisher then needs for the chunks that waited for their ids, so the sort
+    // is launched first and the heavy run table right behind it.  On the stream path the
+    // heavy chains bound the step and go first.  (CASIM_SORT_FIRST=1 / 0 forces either.)
+    const char* sf_env = knob_env("CASIM_SORT_FIRST");
+    const bool sort_first = sf_env ? atoi(sf_env) != 0 : table_chain;
+    const bool sort_after_heavy = split && p->total > 0 && p->bucket && !sort_first;
     if (!go_sort_queued && !sort_after_heavy) {
         int rcs;
         if ((rcs = launch_go_sort()) != CA_OK) return rcs;
@@ -3182,10 +3294,12 @@ int plan_run(ca_estimate_plan* p, const ca_limiter* lim, int32_t* last_index, ca
                                    p->d_rstart.as<int32_t>(), p->d_rsp.as<StreamPod>(), p->d_unsup.as<uint32_t>(), gm,
                                    fast_init ? p->d_lin.as<int32_t>() : nullptr, p->d_need.as<uint8_t>(), lin0);
                 CA_HIP_CHECK(hipGetLastError());
-                hipLaunchKernelGGL(k_emit_runs, dim3(blocks, ng), dim3(256), 0, ss, p->d_meta.as<GroupMeta>(),
-                                   p->d_rstart.as<int32_t>(), p->d_rsp.as<StreamPod>(), U, p->d_stream.as<StreamPod>(),
-                                   p->d_heads.as<uint64_t>(), gm, batch_runs ? 0 : 1);
-                CA_HIP_CHECK(hipGetLastError());
+                if (!table_chain) {     // (the run-table chain reads the table, not the stream)
+                    hipLaunchKernelGGL(k_emit_runs, dim3(blocks, ng), dim3(256), 0, ss, p->d_meta.as<GroupMeta>(),
+                                       p->d_rstart.as<int32_t>(), p->d_rsp.as<StreamPod>(), U,
+                                       p->d_stream.as<StreamPod>(), p->d_heads.as<uint64_t>(), gm, batch_runs ? 0 : 1);
+                    CA_HIP_CHECK(hipGetLastError());
+                }
                 if (events && p->phase_events) CA_HIP_CHECK(hipEventRecord(p->ev[ca_estimate_plan::EV_MERGE], ss));
                 return CA_OK;
             }
@@ -3322,14 +3436,14 @@ int plan_run(ca_estimate_plan* p, const ca_limiter* lim, int32_t* last_index, ca
         // the two kernels are serialised — it must give up at its start deadline
         auto launch_pub = [&](hipStream_t ps) -> int {
             if (sched16)
-                hipLaunchKernelGGL(k_publish<uint16_t>, dim3(std::min(round_tickets, pub_blocks(decoupled))), dim3(256), 0, ps,
+                hipLaunchKernelGGL(k_publish<uint16_t>, dim3(std::min(round_tickets, pub_blocks(decoupled, table_chain))), dim3(256), 0, ps,
                                    p->d_meta.as<GroupMeta>(), p->d_out.as<ChainOut>(), p->d_seg.as<Seg>(),
                                    ids_src, p->d_sched_pod.as<int32_t>(), p->d_tickets.as<int64_t>(),
                                    p->d_qctl.as<int32_t>(), round_tickets, p->nsub, p->d_prog.as<int2>(), p->pch,
                                    reinterpret_cast<uint16_t*>(publish), pub_start_ticks(),
                                    decoupled ? p->d_ids_ready.as<int32_t>() : nullptr, p->ids_epoch, p->h_qc.as<int32_t>());
             else
-                hipLaunchKernelGGL(k_publish<int32_t>, dim3(std::min(round_tickets, pub_blocks(decoupled))), dim3(256), 0, ps,
+                hipLaunchKernelGGL(k_publish<int32_t>, dim3(std::min(round_tickets, pub_blocks(decoupled, table_chain))), dim3(256), 0, ps,
                                    p->d_meta.as<GroupMeta>(), p->d_out.as<ChainOut>(), p->d_seg.as<Seg>(),
                                    ids_src, p->d_sched_pod.as<int32_t>(), p->d_tickets.as<int64_t>(),
                                    p->d_qctl.as<int32_t>(), round_tickets, p->nsub, p->d_prog.as<int2>(), p->pch,
@@ -3345,9 +3459,12 @@ int plan_run(ca_estimate_plan* p, const ca_limiter* lim, int32_t* last_index, ca
         }
         if (p->phase_events) CA_HIP_CHECK(hipEventRecord(p->ev[ca_estimate_plan::EV_CHAIN0], st));
         const bool ps = p->use_ports || p->use_scalar;
-        auto chain_kernel = grows ? (ps ? k_ffd_chain<true, true> : k_ffd_chain<true, false>)
-                                  : (ps ? k_ffd_chain<false, true> : k_ffd_chain<false, false>);
-        if (!grows) {
+        auto chain_kernel =
+            table_chain ? (grows ? (ps ? k_ffd_chain<true, true, true> : k_ffd_chain<true, false, true>)
+                                 : (ps ? k_ffd_chain<false, true, true> : k_ffd_chain<false, false, true>))
+                        : (grows ? (ps ? k_ffd_chain<true, true, false> : k_ffd_chain<true, false, false>)
+                                 : (ps ? k_ffd_chain<false, true, false> : k_ffd_chain<false, false, false>));
+        if (lds > 0) {
             int rcl;
             if ((rcl = ensure_dyn_lds((const void*)chain_kernel, lds)) != CA_OK) return rcl;
         }
@@ -3363,7 +3480,8 @@ int plan_run(ca_estimate_plan* p, const ca_limiter* lim, int32_t* last_index, ca
                                p->d_qctl.as<int32_t>(), p->nsub, p->d_prog.as<int2>(), p->pch, p->d_out.as<ChainOut>(),
                                gm, grows ? p->d_slab.as<unsigned char>() : nullptr,
                                grows ? p->d_slab_off.as<int64_t>() : nullptr, grows ? p->d_gkcap.as<int32_t>() : nullptr,
-                               decoupled ? 1 : 0, p->h_out.as<ChainOut>(), p->h_qc.as<int32_t>());
+                               decoupled ? 1 : 0, p->h_out.as<ChainOut>(), p->h_qc.as<int32_t>(),
+                               p->d_rstart.as<int32_t>(), p->d_rsp.as<StreamPod>(), p->s->n_cls, (int32_t)tab_off);
             CA_HIP_CHECK(hipGetLastError());
             return CA_OK;
         };
@@ -3672,10 +3790,11 @@ int ca_estimate_plan_stats(const ca_estimate_plan* p, int32_t* rounds, float* ch
 
 int ca_estimate_plan_timings(const ca_estimate_plan* p, float* out, int32_t cap) {
     if (!p || (cap > 0 && !out)) return CA_EINVAL;
-    const int32_t n = 9;
+    const int32_t n = 10;
     for (int32_t i = 0; i < 7 && i < cap; i++) out[i] = p->t_ms[i];
     if (cap > 7) out[7] = (float)p->pub_state;
     if (cap > 8) out[8] = (float)p->ran_decoupled;
+    if (cap > 9) out[9] = (float)p->ran_table_chain;
     return n;
 }
 

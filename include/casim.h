@@ -435,7 +435,10 @@ int ca_estimate_plan_stats(const ca_estimate_plan* p, int32_t* rounds, float* ch
  * zero-copy while they ran, 2 the publisher gave up (kernels serialised, or a chain
  * died) and the results were copied instead; [8] 1 if the run took the decoupled Go
  * order (chains on the stable class order, Go's ids beside them: uniform classes and no
- * two classes of a group with equal scores), else 0.  Writes min(cap, 9) values; returns 9. */
+ * two classes of a group with equal scores), else 0; [9] 1 if the decoupled chains walked
+ * the per-class run table in LDS (no stream emission: run batching on, and the table of
+ * the podset's score classes fits the chain's LDS beside its rows), else 0 — the chains
+ * read the emitted stream.  Writes min(cap, 10) values; returns 10. */
 int ca_estimate_plan_timings(const ca_estimate_plan* p, float* out, int32_t cap);
 /* Record the per-phase timing events of later runs (on: default) or not: 8 event records
  * per run on the host's launch path; with them off, ca_estimate_plan_timings[0..5] and the
