@@ -7,10 +7,13 @@
 //
 // Pipeline of one headline step (C2: uniform score classes, no cross-class float64 ties —
 // the decoupled Go order):
-//   st3 (high priority)  k_pdq_sort      Go 1.19 sort.Slice's exact permutation of every
-//                                        group (class ranks folded in), one 1024-thread
-//                                        workgroup per group; writes the Go-order pod ids
-//                                        and an epoch-stamped ready flag per group.
+//   st3 (high priority)  k_pdq_sort      Go 1.19 sort.Slice's exact permutation (class ranks
+//                                        folded in), one 1024-thread workgroup per sort
+//                                        class — the groups with equal pod lists and equal
+//                                        class ranks on their templates (sort_classes) —
+//                                        run for the class's first group; writes the
+//                                        Go-order pod ids and that group's epoch-stamped
+//                                        ready flag, which the other members' consumers read.
 //   st  (heavy groups)   k_run_table     class ranks + per-class counts of each group's
 //                                        list, each rank's first stream position, the
 //                                        class's stream record against the template.
@@ -39,7 +42,10 @@
 
 #include <cstring>
 #include <algorithm>
+#include <atomic>
 #include <functional>
+#include <map>
+#include <tuple>
 #include <chrono>
 #include <mutex>
 #include <thread>
@@ -87,10 +93,11 @@ struct alignas(16) GroupMeta {
     int32_t tmpl;                  // template index
     uint32_t tflags;               // NF_* of the template
     int32_t moff;                  // offset of the group's 64-pod head masks
-    int32_t toff;                  // unused (was: compaction tile counters)
+    int32_t ids_off;               // decoupled Go order: offset of the group's ids in d_spod_go — its own `off`,
+                                   // or that of the group whose sort it shares (sort_classes)
     int32_t hoff;                  // offset of the group's radix histograms [256][rtiles]
     int32_t rtiles;                // radix tiles of the group (bucket sort)
-    int32_t pad;
+    int32_t ids_grp;               // ... and the group whose ready flag covers those ids (itself, or that group)
 };
 static_assert(sizeof(GroupMeta) == 64, "GroupMeta");
 // Group handled by a block: the launch's group map (a subset of the batch, e.g. the
@@ -891,37 +898,18 @@ __global__ void __launch_bounds__(pdq::NT) k_pdq_sort(const GroupMeta* __restric
         const uint64_t t_k2 = clock64();
 #endif
         if (ids_out) {
-            // decoupled Go order: the pod ids in sorted order.  A gather pod_idx[off +
-            // e16[k]] straight from memory was ~40 % of the slowest workgroup's time on C2
-            // (random 4-byte reads, every group at once); instead the group's list goes
-            // through the LDS the sort no longer needs (the rank bytes and the partition
-            // bitmaps) in coalesced slices, and each pass picks the sorted positions that
-            // fall in its slice.
-            int32_t* const buf = reinterpret_cast<int32_t*>(rk);
-            // (npad >= 64: at least 16 entries per slice)
-            const int32_t cap = (int32_t)((npad + (npad / 64) * 10) / 4);
-            for (int32_t lo = 0; lo < n; lo += cap) {
-                const int32_t hi = min(n, lo + cap);
-                __syncthreads();                       // (the previous slice is consumed)
-                constexpr int SL = 16;                 // a slice is one round of loads per thread
-                for (int32_t j0 = lo + tid; j0 < hi; j0 += pdq::NT * SL) {
-                    int32_t v[SL];
+            // decoupled Go order: the pod ids in sorted order, gathered straight from the
+            // group's list (pod_idx[off + e16[k]], PDQ_UB positions per thread in flight).
+            // With the stream chains this gather was ~40 % of the slowest workgroup's time on
+            // C2 and the list went through LDS in coalesced slices instead; with the run-table
+            // chains (no stream traffic beside the sort) the gather is the faster of the two,
+            // with one workgroup per group as with shared sorts (profiles/sort_share_ab.txt).
+            for (int32_t k0 = tid; k0 < n; k0 += pdq::NT * PDQ_UB) {
+                int32_t v[PDQ_UB];
 #pragma unroll
-                    for (int u = 0; u < SL; u++) {
-                        const int32_t j = j0 + u * pdq::NT;
-                        v[u] = j < hi ? pod_idx[off + j] : 0;
-                    }
+                for (int u = 0; u < PDQ_UB; u++) { const int32_t k = k0 + u * pdq::NT; v[u] = k < n ? pod_idx[off + (int32_t)e16[k]] : 0; }
 #pragma unroll
-                    for (int u = 0; u < SL; u++) {
-                        const int32_t j = j0 + u * pdq::NT;
-                        if (j < hi) buf[j - lo] = v[u];
-                    }
-                }
-                __syncthreads();
-                for (int32_t k = tid; k < n; k += pdq::NT) {
-                    const int32_t pos = e16[k];
-                    if (pos >= lo && pos < hi) ids_out[off + k] = buf[pos - lo];
-                }
+                for (int u = 0; u < PDQ_UB; u++) { const int32_t k = k0 + u * pdq::NT; if (k < n) ids_out[off + k] = v[u]; }
             }
         } else
             for (int32_t k = tid; k < n; k += pdq::NT) sorted[off + k] = e16[k];
@@ -1467,7 +1455,9 @@ __global__ void __launch_bounds__(256) k_publish(const GroupMeta* __restrict__ g
                     __builtin_amdgcn_s_sleep(2);
                 }
                 if (tk >= 0 && ids_ready) {                  // the group's Go-order ids
-                    const int32_t g = (int32_t)(uint32_t)(tk & 0xFFFFFFFFll) / nsub;
+                    // (the flag of the group whose sort wrote them: the group's own, or the
+                    // representative of its sort class)
+                    const int32_t g = groups[(int32_t)(uint32_t)(tk & 0xFFFFFFFFll) / nsub].ids_grp;
                     for (;;) {
                         if (__hip_atomic_load(&ids_ready[g], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == ids_epoch) {
                             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
@@ -1506,13 +1496,14 @@ __global__ void __launch_bounds__(256) k_publish(const GroupMeta* __restrict__ g
         const int32_t g = tk / nsub, sub = tk - g * nsub;
         const GroupMeta gm = groups[g];
         const Seg* gs = segs + gm.off;
+        const int32_t soff = ids_ready ? gm.ids_off : gm.off;       // the group's pod ids in spod
         const int32_t a = sub * pch, b = min(gm.count, a + pch);
         if (pure_off >= 0) {
             // one contiguous copy: 16-byte stores into the page-locked buffer (fewer, fuller
             // PCIe writes), scalar stores for the unaligned head and tail
             constexpr int V = 16 / (int)sizeof(T);
             T* const dst = pub + gm.off;
-            const int32_t* const src = spod + gm.off + pure_off;
+            const int32_t* const src = spod + soff + pure_off;
             int32_t h = a;
             while (h < b && ((uintptr_t)(dst + h) & 15u)) h++;                 // aligned from h on
             const int32_t nv = (b - h) / V;
@@ -1584,8 +1575,8 @@ __global__ void __launch_bounds__(256) k_publish(const GroupMeta* __restrict__ g
                 }
             }
             for (int32_t i = at + (int32_t)threadIdx.x; i < lim; i += blockDim.x)
-                pub[gm.off + i] = (T)(from_seg ? spod[gm.off + src_off + i]
-                                               : ids_ready ? spod[gm.off + ld_coh(sched_dev + gm.off + i)]
+                pub[gm.off + i] = (T)(from_seg ? spod[soff + src_off + i]
+                                               : ids_ready ? spod[soff + ld_coh(sched_dev + gm.off + i)]
                                                            : sched_dev[gm.off + i]);
             at = lim;
         }
@@ -2503,7 +2494,7 @@ __global__ void __launch_bounds__(256) k_copy_segments(const GroupMeta* __restri
     const int32_t nseg = o.status == CA_OK ? o.nseg : 0;
     const Seg* gs = segs + gm.off;
     int32_t* sp = sched_pod + gm.off;
-    const int32_t* src = spod + gm.off;
+    const int32_t* src = spod + (map_singles ? gm.ids_off : gm.off);   // (decoupled: maybe a shared sort's ids)
     // past n_scheduled (or a failed group): -1, also over what an earlier speculation
     // round of the group wrote
     for (int32_t i = max(base, ns) + (int32_t)threadIdx.x; i < end; i += blockDim.x) {
@@ -2559,6 +2550,10 @@ struct ca_estimate_plan {
     DevBuf d_rstart, d_rsp;        // decoupled: per group, each rank's first stream position and record
     DevBuf d_item_cls;             // bucket path: the score class of every (group, pod) item, uploaded with the lists
     int32_t ids_epoch = 0;
+    // shared sorts (sort_classes): the number of sort classes — when below G their
+    // representatives, in group order, follow the G records of d_meta as k_pdq_sort's group
+    // map — and the number of sorts the last run launched
+    int32_t n_sorts = 0, ran_sorts = 0;
     hipStream_t st3 = nullptr;
     hipEvent_t ev_emitA = nullptr, ev_emitB = nullptr, ev_ids = nullptr;
     // HBM-slab rows (k_ffd_chain<true>): per group kcap and slab offset, for the limiter
@@ -2730,6 +2725,118 @@ bool groups_tie_free(const ca_podset* s, const int32_t* pod_idx, const std::vect
     return true;
 }
 
+// Sort classes of the decoupled Go order.  k_pdq_sort's permutation of a
+// group is a function of its pod list and of the dense ranks of the podset's classes on its
+// template, and its ids of the list alone besides: two groups with element-wise equal
+// pod_idx slices and equal rank vectors over all U classes (same float64 operations and the
+// same dense rank as block_class_rank) get the same ids, so one sort serves both.  rep[g] =
+// the first group, in group order, of g's class (g itself when it shares with nobody);
+// returns the number of classes.  Equality is exact: the signature (count, rank vector,
+// a strided sample of the list) only groups the candidates, every match is a full
+// comparison of the lists.  The rank vectors cost G * U log U on the host, so a batch with
+// G * U above SHARE_MAX_GU keeps one sort per group.  `side` is run once, beside the
+// comparisons when they go to the host's workers.
+constexpr int64_t SHARE_MAX_GU = 1 << 17;
+int32_t sort_classes(const ca_podset* s, const int32_t* pod_idx, const std::vector<GroupMeta>& meta,
+                     const ca_template* templates, std::vector<int32_t>& rep, const std::function<void()>& side) {
+    const int32_t G = (int32_t)meta.size(), U = s->n_cls;
+    rep.resize((size_t)G);
+    for (int32_t g = 0; g < G; g++) rep[g] = g;
+    if (G < 2 || (int64_t)G * std::max(U, 1) > SHARE_MAX_GU) { side(); return G; }
+    // the rank vector of every distinct (cpu, memory) allocatable, then the distinct vectors
+    std::map<std::pair<int64_t, int64_t>, int32_t> by_alloc;
+    std::map<std::vector<int32_t>, int32_t> by_ranks;
+    std::vector<int32_t> rv((size_t)G);
+    std::vector<std::pair<uint64_t, int32_t>> key((size_t)U);
+    std::vector<int32_t> ranks((size_t)U);
+    for (int32_t g = 0; g < G; g++) {
+        const ca_template& tp = templates[meta[g].tmpl];
+        const int64_t acpu = tp.node.alloc_milli_cpu, amem = tp.node.alloc_memory;
+        const auto it = by_alloc.find({acpu, amem});
+        if (it != by_alloc.end()) { rv[g] = it->second; continue; }
+        for (int32_t c = 0; c < U; c++) {
+            double score = 0.0;               // calculatePodScore, as block_class_rank / groups_tie_free
+            if (acpu > 0) score += (double)s->h_cls_sc[2 * c] / (double)acpu;
+            if (amem > 0) score += (double)s->h_cls_sc[2 * c + 1] / (double)amem;
+            if (score == 0.0) score = 0.0;    // -0 == +0 (ordered_bits)
+            uint64_t b;
+            std::memcpy(&b, &score, sizeof b);
+            b = (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+            key[c] = {~b, c};                 // ascending key == descending score
+        }
+        std::sort(key.begin(), key.end());
+        int32_t dense = 0;
+        for (int32_t i = 0; i < U; i++) {
+            if (i > 0 && key[i].first != key[i - 1].first) dense++;
+            ranks[key[i].second] = dense;
+        }
+        const int32_t id = by_ranks.emplace(ranks, (int32_t)by_ranks.size()).first->second;
+        by_alloc.emplace(std::make_pair(acpu, amem), id);
+        rv[g] = id;
+    }
+    // candidates: same count, same rank vector, same sample of the list
+    constexpr int32_t NS = 8;                         // (few: every sample of a cold list is a cache miss)
+    std::map<std::tuple<int32_t, int32_t, uint64_t>, std::vector<int32_t>> cand;
+    for (int32_t g = 0; g < G; g++) {
+        const int32_t n = meta[g].count;
+        const int32_t* l = pod_idx + meta[g].off;
+        uint64_t h = 0x9E3779B97F4A7C15ull;
+        const int32_t step = std::max(1, n / NS);
+        for (int32_t i = 0; i < n; i += step) h = (h ^ (uint32_t)l[i]) * 0x100000001B3ull;
+        if (n > 0) h = (h ^ (uint32_t)l[n - 1]) * 0x100000001B3ull;
+        cand[std::make_tuple(n, rv[g], h)].push_back(g);
+    }
+    // the first group of a bucket is a representative; the others are compared with it, every
+    // pair of every bucket in one pass over the host's workers (task 0 runs `side` first: the
+    // caller's list upload, which then overlaps the comparisons)
+    struct Pair { int32_t head, g; size_t bytes; };
+    std::vector<Pair> pairs;
+    size_t pair_bytes = 0;
+    for (auto& kv : cand) {
+        const std::vector<int32_t>& v = kv.second;        // (ascending group order)
+        const size_t bytes = sizeof(int32_t) * (size_t)std::get<0>(kv.first);
+        for (size_t k = 1; k < v.size(); k++) { pairs.push_back({v[0], v[k], bytes}); pair_bytes += bytes; }
+    }
+    std::vector<uint8_t> same(pairs.size(), 0);
+    auto compare = [&](size_t k) {
+        const Pair& q = pairs[k];
+        same[k] = q.bytes == 0 || std::memcmp(pod_idx + meta[q.head].off, pod_idx + meta[q.g].off, q.bytes) == 0;
+    };
+    if (pair_bytes < ((size_t)1 << 18)) {
+        side();
+        for (size_t k = 0; k < pairs.size(); k++) compare(k);
+    } else {
+        std::atomic<size_t> next{0};
+        casim::parallel_run(8, [&](int32_t t) {
+            if (t == 0) side();
+            for (size_t k; (k = next.fetch_add(1, std::memory_order_relaxed)) < pairs.size();) compare(k);
+        });
+    }
+    for (size_t k = 0; k < pairs.size(); k++)
+        if (same[k]) rep[pairs[k].g] = pairs[k].head;
+    // a candidate unequal to its bucket's first group (the signature matched, the lists differ):
+    // those go round among themselves
+    int32_t classes = 0;
+    for (auto& kv : cand) {
+        std::vector<int32_t> v;
+        for (size_t k = 0; k < kv.second.size(); k++)
+            if (k == 0 || rep[kv.second[k]] == kv.second[k]) v.push_back(kv.second[k]);
+        const size_t bytes = sizeof(int32_t) * (size_t)std::get<0>(kv.first);
+        classes++;                                        // (v[0] and the groups equal to it)
+        v.erase(v.begin());
+        while (!v.empty()) {
+            classes++;
+            std::vector<int32_t> rest;
+            for (size_t k = 1; k < v.size(); k++) {
+                if (std::memcmp(pod_idx + meta[v[0]].off, pod_idx + meta[v[k]].off, bytes) == 0) rep[v[k]] = v[0];
+                else rest.push_back(v[k]);
+            }
+            v.swap(rest);
+        }
+    }
+    return classes;
+}
+
 int plan_prepare(ca_estimate_plan* p, ca_mirror* m, const ca_podset* s, const int32_t* group_off,
                  const int32_t* pod_idx, const ca_template* templates, int32_t G) {
     p->m = m; p->s = s; p->G = G;
@@ -2776,10 +2883,10 @@ int plan_prepare(ca_estimate_plan* p, ca_mirror* m, const ca_podset* s, const in
         gm.tmpl = g;
         gm.tflags = t.node.flags;
         gm.moff = p->n_masks;
-        gm.toff = p->n_tiles;
+        gm.ids_off = gm.off;
         gm.rtiles = (c + RT - 1) / RT;
         gm.hoff = p->n_hist;
-        gm.pad = 0;
+        gm.ids_grp = g;
         p->n_hist += 256 * gm.rtiles;
         p->max_rtiles = std::max(p->max_rtiles, gm.rtiles);
         p->n_masks += (c + 63) / 64;
@@ -2791,14 +2898,38 @@ int plan_prepare(ca_estimate_plan* p, ca_mirror* m, const ca_podset* s, const in
     hipStream_t st = m->stream;
     int rc;
     const size_t tot = (size_t)std::max(p->total, 1);
+    // The sort classes first (sort_classes; CASIM_SORT_SHARE=0: one sort per group, for tests
+    // and A/B): groups with equal lists also share what the pass below finds, so it walks
+    // each class's first group only — a comparison of two lists costs far less per item than
+    // the walk's lookups.
+    std::vector<int32_t> sort_rep;
+    int32_t n_classes = G;
+    // (the list upload is queued by the caller's thread beside the comparisons, or beside the
+    // walk below when there are none)
+    hipError_t ce = hipSuccess;
+    rc = CA_OK;
+    bool uploaded = false;
+    auto upload = [&]() {
+        if ((rc = p->d_pod_idx.reserve(sizeof(int32_t) * tot)) == CA_OK && p->total)
+            ce = hipMemcpyAsync(p->d_pod_idx.ptr, pod_idx, sizeof(int32_t) * p->total, hipMemcpyHostToDevice, st);
+        uploaded = true;
+    };
+    if (p->bucket && s->cls_uniform && p->total > 0 &&
+        !(knob_env("CASIM_SORT_SHARE") && atoi(knob_env("CASIM_SORT_SHARE")) == 0))
+        n_classes = sort_classes(s, pod_idx, p->h_meta, templates, sort_rep, upload);
+    if (n_classes == G) sort_rep.clear();
     // One pass over the lists (per-pod summaries of the podset: compact arrays instead of
     // the 208-B records), split over host threads for big batches: index validation, the
     // port / extended-resource flags and each group's summed requests for the demand
     // order.  The lists travel to the device meanwhile (the caller's thread queues the copy);
     // the item classes are gathered there from the podset's class column (k_item_cls).
     {
-        const int32_t total = p->total;
-        const int32_t T = std::max(1, std::min(7, total / (1 << 17)));
+        // the groups walked and the prefix of their counts: the walk's items, split evenly
+        std::vector<int32_t> wg, woff(1, 0);
+        for (int32_t g = 0; g < G; g++)
+            if (sort_rep.empty() || sort_rep[g] == g) { wg.push_back(g); woff.push_back(woff.back() + p->h_meta[g].count); }
+        const int32_t K = (int32_t)wg.size(), wtotal = woff.back();
+        const int32_t T = std::max(1, std::min(7, wtotal / (1 << 17)));
         struct Part { bool bad = false; uint8_t fl = 0; std::vector<double> c, mm; };
         std::vector<Part> part((size_t)T);
         const bool want_fl = s->any_ports || s->any_scalar;
@@ -2806,13 +2937,15 @@ int plan_prepare(ca_estimate_plan* p, ca_mirror* m, const ca_podset* s, const in
             Part& pt = part[(size_t)t];
             pt.c.assign((size_t)G, 0.0);
             pt.mm.assign((size_t)G, 0.0);
-            const int32_t a = (int32_t)((int64_t)total * t / T), b = (int32_t)((int64_t)total * (t + 1) / T);
-            int32_t g = (int32_t)(std::upper_bound(group_off, group_off + G + 1, a) - group_off) - 1;
+            const int32_t a = (int32_t)((int64_t)wtotal * t / T), b = (int32_t)((int64_t)wtotal * (t + 1) / T);
+            int32_t k0 = std::max(0, (int32_t)(std::upper_bound(woff.begin(), woff.end(), a) - woff.begin()) - 1);
             const int32_t np_ = s->t.n_pods;
             const int64_t* req = s->h_req.data();
-            for (int32_t i = a; i < b && !pt.bad;) {
-                while (g < G - 1 && group_off[g + 1] <= i) g++;
-                const int32_t e = std::min(b, group_off[g + 1]);
+            for (int32_t v = a; v < b && !pt.bad;) {       // v: position in the walked groups' items
+                while (k0 < K - 1 && woff[(size_t)k0 + 1] <= v) k0++;
+                const int32_t g = wg[(size_t)k0];
+                const int32_t i = group_off[g] + (v - woff[(size_t)k0]);
+                const int32_t e = group_off[g] + (std::min(b, woff[(size_t)k0 + 1]) - woff[(size_t)k0]);
                 double c0 = 0, c1 = 0, m0 = 0, m1 = 0;   // (two chains each: the adds pipeline)
                 bool bad = false;
                 int32_t k = i;
@@ -2833,17 +2966,13 @@ int plan_prepare(ca_estimate_plan* p, ca_mirror* m, const ca_podset* s, const in
                     for (int32_t q = i; q < e; q++) pt.fl |= s->h_pflags[pod_idx[q]];
                 pt.c[(size_t)g] += c0 + c1;
                 pt.mm[(size_t)g] += m0 + m1;
-                i = e;
+                v += e - i;
             }
         };
-        hipError_t ce = hipSuccess;
-        rc = CA_OK;
-        // task 0 (the caller's thread) queues the list upload, tasks 1..T walk the items
-        casim::parallel_run(T + 1, [&](int32_t t) {
-            if (t > 0) { work(t - 1); return; }
-            if ((rc = p->d_pod_idx.reserve(sizeof(int32_t) * tot)) == CA_OK && total)
-                ce = hipMemcpyAsync(p->d_pod_idx.ptr, pod_idx, sizeof(int32_t) * total, hipMemcpyHostToDevice, st);
-        });
+        // task 0 (the caller's thread) queues the list upload if it is not queued yet,
+        // tasks 1..T walk the items
+        if (uploaded) casim::parallel_run(T, work);
+        else casim::parallel_run(T + 1, [&](int32_t t) { if (t > 0) work(t - 1); else upload(); });
         if (rc != CA_OK) return rc;
         CA_HIP_CHECK(ce);
         bool bad = false;
@@ -2859,6 +2988,10 @@ int plan_prepare(ca_estimate_plan* p, ca_mirror* m, const ca_podset* s, const in
             CA_HIP_CHECK(hipStreamSynchronize(st));    // (the list copy may still read pod_idx)
             return CA_EINVAL;
         }
+        for (int32_t g = 0; g < G && !sort_rep.empty(); g++) {      // equal lists, equal sums
+            c[(size_t)g] = c[(size_t)sort_rep[g]];
+            mm[(size_t)g] = mm[(size_t)sort_rep[g]];
+        }
         for (int32_t g = 0; g < G; g++) {
             const GroupMeta& gm = p->h_meta[g];
             double d = gm.tpods > 0 ? (double)gm.count / gm.tpods : 0.0;
@@ -2868,7 +3001,25 @@ int plan_prepare(ca_estimate_plan* p, ca_mirror* m, const ca_podset* s, const in
         }
     }
     p->decouple_ok = p->bucket && s->cls_uniform && groups_tie_free(s, pod_idx, p->h_meta, templates);
-    if ((rc = p->d_meta.reserve(sizeof(GroupMeta) * (size_t)std::max(G, 1))) != CA_OK) return rc;
+    // decoupled: one Go-order sort per sort class; the members read their representative's ids
+    // and wait on its ready flag
+    p->n_sorts = G;
+    std::vector<int32_t> sort_map;                    // (alive until the uploads below are done)
+    if (p->decouple_ok && !sort_rep.empty()) {
+        p->n_sorts = n_classes;
+        {
+            for (int32_t g = 0; g < G; g++) {
+                p->h_meta[g].ids_grp = sort_rep[g];
+                p->h_meta[g].ids_off = p->h_meta[sort_rep[g]].off;
+                if (sort_rep[g] == g) sort_map.push_back(g);
+            }
+        }
+    }
+    if ((rc = p->d_meta.reserve(sizeof(GroupMeta) * (size_t)std::max(G, 1) + sizeof(int32_t) * sort_map.size())) != CA_OK)
+        return rc;
+    if (!sort_map.empty())
+        CA_HIP_CHECK(hipMemcpyAsync(p->d_meta.as<GroupMeta>() + G, sort_map.data(), sizeof(int32_t) * sort_map.size(),
+                                    hipMemcpyHostToDevice, st));
     if ((rc = p->d_tmpl.reserve(sizeof(ca_template) * (size_t)std::max(G, 1))) != CA_OK) return rc;
     if ((rc = p->d_sortA.reserve(sizeof(SortItem) * tot)) != CA_OK) return rc;
     if ((rc = p->d_sortB.reserve(sizeof(SortItem) * tot)) != CA_OK) return rc;
@@ -3119,6 +3270,7 @@ int plan_run(ca_estimate_plan* p, const ca_limiter* lim, int32_t* last_index, ca
     const bool decoupled = go_order && p->decouple_ok && p->total > 0 &&
                            !(knob_env("CASIM_GO_DECOUPLE") && atoi(knob_env("CASIM_GO_DECOUPLE")) == 0);
     p->ran_decoupled = decoupled ? 1 : 0;
+    p->ran_sorts = G;                                   // (decoupled: the sort classes, launch_go_sort)
     // Go's sort.Slice permutation of every group and its pod ids, on st3: its own class
     // ranks, k_pdq_sort, ids into d_spod_go and per-group ready flags holding this run's
     // epoch (no reset between runs; every run is synchronised before it returns).  The
@@ -3142,14 +3294,19 @@ int plan_run(ca_estimate_plan* p, const ca_limiter* lim, int32_t* last_index, ca
         // the class ranks inside the sort kernel when its LDS has room for the scratch
         const size_t npad = ((size_t)std::min(p->max_count, PDQ_LDS_N) + 63) & ~(size_t)63;
         const bool fold = 16 * (size_t)NP <= 3 * npad && 2 * (size_t)U <= npad / 8 && !knob_env("CASIM_NO_RANK_FOLD");
+        // one workgroup per sort class (its representative group); the other members' consumers
+        // read the representative's slice of d_spod_go and its ready flag (GroupMeta::ids_off / ids_grp)
+        const int32_t ns = p->n_sorts;
+        const int32_t* smap = ns < G ? reinterpret_cast<const int32_t*>(p->d_meta.as<GroupMeta>() + G) : nullptr;
+        p->ran_sorts = ns;
         if (!fold) {
-            hipLaunchKernelGGL(k_class_rank, dim3(G), dim3(1024), 0, p->st3, p->d_meta.as<GroupMeta>(),
+            hipLaunchKernelGGL(k_class_rank, dim3(ns), dim3(1024), 0, p->st3, p->d_meta.as<GroupMeta>(),
                                p->d_tmpl.as<ca_template>(), p->s->d_cls_sc.as<int64_t>(), U, NP,
-                               p->d_crank2.as<int32_t>(), (const int32_t*)nullptr);
+                               p->d_crank2.as<int32_t>(), smap);
             CA_HIP_CHECK(hipGetLastError());
         }
         int rc0;
-        if ((rc0 = launch_pdq_sort(p, p->st3, nullptr, G, p->d_crank2.as<int32_t>(), U, nullptr, 0,
+        if ((rc0 = launch_pdq_sort(p, p->st3, smap, ns, p->d_crank2.as<int32_t>(), U, nullptr, 0,
                                    p->d_sortC.as<uint32_t>(), p->d_spod_go.as<int32_t>(),
                                    p->d_ids_ready.as<int32_t>(), p->ids_epoch, fold ? NP : 0)) != CA_OK)
             return rc0;
@@ -3790,11 +3947,12 @@ int ca_estimate_plan_stats(const ca_estimate_plan* p, int32_t* rounds, float* ch
 
 int ca_estimate_plan_timings(const ca_estimate_plan* p, float* out, int32_t cap) {
     if (!p || (cap > 0 && !out)) return CA_EINVAL;
-    const int32_t n = 10;
+    const int32_t n = 11;
     for (int32_t i = 0; i < 7 && i < cap; i++) out[i] = p->t_ms[i];
     if (cap > 7) out[7] = (float)p->pub_state;
     if (cap > 8) out[8] = (float)p->ran_decoupled;
     if (cap > 9) out[9] = (float)p->ran_table_chain;
+    if (cap > 10) out[10] = (float)p->ran_sorts;
     return n;
 }
 

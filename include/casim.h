@@ -438,7 +438,10 @@ int ca_estimate_plan_stats(const ca_estimate_plan* p, int32_t* rounds, float* ch
  * two classes of a group with equal scores), else 0; [9] 1 if the decoupled chains walked
  * the per-class run table in LDS (no stream emission: run batching on, and the table of
  * the podset's score classes fits the chain's LDS beside its rows), else 0 — the chains
- * read the emitted stream.  Writes min(cap, 10) values; returns 10. */
+ * read the emitted stream; [10] the Go-order sorts the run launched: groups with equal pod
+ * lists whose templates rank the podset's score classes alike share one on the decoupled
+ * path (CASIM_SORT_SHARE=0: one per group), otherwise the number of groups.  Writes
+ * min(cap, 11) values; returns 11. */
 int ca_estimate_plan_timings(const ca_estimate_plan* p, float* out, int32_t cap);
 /* Record the per-phase timing events of later runs (on: default) or not: 8 event records
  * per run on the host's launch path; with them off, ca_estimate_plan_timings[0..5] and the
