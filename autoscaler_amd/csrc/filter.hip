@@ -1,5 +1,7 @@
 // filter.hip — FilterOutSchedulable: HintingSimulator.TrySchedulePods(pending pods,
-// ScheduleAnywhere, breakOnFailure=false), committed into the mirror.
+// ScheduleAnywhere, breakOnFailure=false), committed into the mirror — and the general
+// TrySchedulePods(pods, isNodeAcceptable, breakOnFailure) of ca_try_schedule_pods, the same
+// kernels with a node mask (one acc bit per node, k_fb_acc) and the break.
 //
 // Reference: CA/core/podlistprocessor/filter_out_schedulable.go:95-124,
 // CA/simulator/scheduling/hinting_simulator.go:58-125 (findNodeWithHints / findNode),
@@ -55,6 +57,7 @@ struct FoCtl {
     int32_t bad_line, bad_val; // CASIM_FO_CHECKS builds: the first index check that failed
     unsigned long long seq_cycles, all_cycles;   // CASIM_PROF builds: wave 0's walk, the whole kernel
     unsigned long long fb_cyc[4];                 // CASIM_PROF builds, bitmap walk: hint, scan, place, batch loads
+    int32_t tried, pad;        // pods processed (P, or up to and including the pod the break stopped at)
 };
 
 struct FoArgs {
@@ -78,6 +81,9 @@ struct FoArgs {
     uint8_t* owner_over;       // per controller: overflowed
     FoCtl* ctl;
     int32_t n_pods, n_classes, n_owners;
+    const uint64_t* acc;       // isNodeAcceptable, one bit per node (k_fb_acc); NULL: every node
+    uint8_t* out_hok;          // per position: the hint passed CheckPredicates (NULL: not wanted)
+    int32_t brk;               // breakOnFailure
 };
 
 // Index checks of the diagnostics build (make checks: -DCASIM_FO_CHECKS): an index out of
@@ -107,12 +113,14 @@ struct SqSmem {
     int32_t slot_out[SQ_SLOTS];      // node of the walked pod, -1 (flushed to HBM per phase)
     uint8_t slot_mark[SQ_SLOTS];     // the class is marked unschedulable
     uint8_t slot_dirty[SQ_SLOTS];
+    uint8_t slot_hok[SQ_SLOTS];      // the hint passed CheckPredicates (accepted or not)
     uint8_t win_dirty[SQ_WIN];
     int32_t L, wb, wn, cur;          // lastIndex; window start position and length; cursor offset
     int32_t k0, ns, j;               // phase: first pod, staged pods, next slot
     int32_t cmd, arg;                // block step the sequencer asks for
     int32_t succ;                    // some scan succeeded (lastIndex moved)
-    uint32_t carry;                  // CMD_RING: evaluations of the window part of the scan
+    int32_t stop;                    // breakOnFailure: slot sm.j - 1 was left without a node, the walk ends
+    uint32_t carry;                 // CMD_RING: evaluations of the window part of the scan
     int32_t red_i[SQ_W];
 };
 
@@ -171,8 +179,11 @@ __device__ inline uint8_t ld_mark(const uint8_t* p) {
 }
 
 // ---- filters ------------------------------------------------------------------------
-// FitsAnyNodeMatching visits the node (schedulerbased.go:116-127): PreFilter's NodeNames
-// and Spec.Unschedulable skip a node without running the filters
+// FitsAnyNodeMatching visits the node (schedulerbased.go:116-127): nodeMatches, PreFilter's
+// NodeNames and Spec.Unschedulable skip a node without running the filters
+__device__ inline bool sq_acc(const FoArgs& a, int32_t pos) {
+    return !a.acc || ((a.acc[pos >> 6] >> (pos & 63)) & 1ull);
+}
 __device__ inline bool sq_visible(const FoArgs& a, const PodHot& p, const ca_pod_spec& s, const NodeHot& h,
                                   const NodeStatic& st) {
     if (h.flags & NF_UNSCHED) return false;
@@ -316,6 +327,7 @@ __device__ __attribute__((always_inline)) void sq_load_slots(const FoArgs& a, Sq
         sm.slot_cls[t] = c;
         sm.slot_mark[t] = (c >= 0) ? ld_mark(&a.cls_mark[CK(c, a.n_classes)]) : 0;
         sm.slot_dirty[t] = 0;
+        sm.slot_hok[t] = 0;
     }
     __syncthreads();
 }
@@ -337,7 +349,7 @@ __device__ __attribute__((always_inline)) void sq_ring_scan(const FoArgs& a, SqS
                 if (pos >= n) pos -= n;
                 pos = CK(pos, n);
                 const NodeHot h = ld_hot_coh(a.hot + pos);
-                const bool v = sq_visible(a, p, s, h, a.st[pos]);
+                const bool v = sq_acc(a, pos) && sq_visible(a, p, s, h, a.st[pos]);
                 vis |= (uint32_t)v << i;
                 if (v) {
                     bool ok;
@@ -375,7 +387,8 @@ __device__ __attribute__((always_inline)) void sq_sequence(const FoArgs& a, SqSm
     const int32_t n = a.n, ns = sm.ns, k0 = sm.k0;
     const int32_t wb = sm.wb, wn = sm.wn;
     int32_t j = sm.j, L = sm.L, cur = sm.cur;
-    bool succ = false;
+    bool succ = false, stop = false;
+    const bool brk = a.brk != 0;
     int32_t cmd = (k0 + ns >= a.P) ? CMD_DONE : CMD_PHASE, arg = 0;
     // lane l holds slot l's scalars; the walk reads them with readlane (no LDS round trip)
     const int ll = lane < ns ? lane : 0;
@@ -405,6 +418,10 @@ __device__ __attribute__((always_inline)) void sq_sequence(const FoArgs& a, SqSm
             bool ok;
             if (inw) ok = sq_fits(a, p, s, sm.win_hot[ho], &sm.win_ext[ho], &sm.win_st[ho], true);
             else ok = sq_fits(a, p, s, sm.slot_hot[j], &sm.slot_ext[j], &sm.slot_st[j], true);
+            if (ok) {                                         // Hints.Set (:95), then isNodeAcceptable (:102):
+                if (lane == 0) sm.slot_hok[j] = 1;            // a node outside the mask sends the pod to the scan
+                ok = sq_acc(a, h);
+            }
             if (ok) {
                 node = h;
                 if (inw) {
@@ -428,7 +445,7 @@ __device__ __attribute__((always_inline)) void sq_sequence(const FoArgs& a, SqSm
             const int32_t c = __builtin_amdgcn_readlane(l_cls, j);
             const bool can_mark = c >= 0 && !(pf & PF_DAEMONSET);
             if ((pf & PF_PREFILTER_FAIL) || n == 0) {          // fails without a scan
-                if (can_mark) {
+                if (can_mark && !brk) {
                     if (lane == 0) sm.slot_out[j] = -1;
                     cmd = CMD_MARK;
                     arg = j++;
@@ -445,7 +462,9 @@ __device__ __attribute__((always_inline)) void sq_sequence(const FoArgs& a, SqSm
                     if (o < lim) {
                         if (o >= wn) o -= wn;
                         const NodeHot hh = sm.win_hot[o];
-                        vis = sq_visible(a, p, s, hh, sm.win_st[o]);
+                        int32_t pos = wb + o;
+                        if (pos >= n) pos -= n;
+                        vis = sq_acc(a, pos) && sq_visible(a, p, s, hh, sm.win_st[o]);
                         fit = vis && sq_fits(a, p, s, hh, &sm.win_ext[o], &sm.win_st[o], false);
                     }
                     const unsigned long long fm = __ballot(fit), vm = __ballot(vis);
@@ -473,7 +492,7 @@ __device__ __attribute__((always_inline)) void sq_sequence(const FoArgs& a, SqSm
                     if (wn == n && cur == n) cur = 0;            // whole ring resident: keep walking
                 } else if (wn == n) {                            // the whole ring: no node fits
                     if (lane == 0) evals += ev;
-                    if (can_mark) {
+                    if (can_mark && !brk) {
                         if (lane == 0) sm.slot_out[j] = -1;
                         cmd = CMD_MARK;
                         arg = j++;
@@ -488,6 +507,12 @@ __device__ __attribute__((always_inline)) void sq_sequence(const FoArgs& a, SqSm
             }
         }
         if (lane == 0) sm.slot_out[j] = node;
+        if (brk && node < 0) {                                   // breakOnFailure (:83-85): the walk ends here
+            j++;
+            stop = true;
+            cmd = CMD_DONE;
+            break;
+        }
     }
     if (lane == 0) {
         sm.j = j;
@@ -496,6 +521,7 @@ __device__ __attribute__((always_inline)) void sq_sequence(const FoArgs& a, SqSm
         sm.cmd = cmd;
         sm.arg = arg;
         if (succ) sm.succ = 1;
+        if (stop) sm.stop = 1;
     }
 }
 
@@ -503,9 +529,11 @@ __device__ __attribute__((always_inline)) void sq_sequence(const FoArgs& a, SqSm
 __device__ inline void sq_flush(const FoArgs& a, SqSmem& sm) {
     const int32_t t = (int32_t)threadIdx.x;
     if (t < sm.ns) {
-        const int32_t k = CK(sm.k0 + t, a.P), node = sm.slot_out[t];
+        const bool walked = !sm.stop || t < sm.j;              // the slots behind a break were not run
+        const int32_t k = CK(sm.k0 + t, a.P), node = walked ? sm.slot_out[t] : -1;
         a.out_node[k] = node;
         if (node >= 0) a.hints[k] = node;
+        if (a.out_hok) a.out_hok[k] = walked ? sm.slot_hok[t] : 0;
     }
 }
 
@@ -527,6 +555,7 @@ __global__ void __launch_bounds__(SQ_T) k_filter_out(FoArgs a) {
         sm.ns = min(SQ_SLOTS, a.P);
         sm.j = 0;
         sm.succ = 0;
+        sm.stop = 0;
         sm.wb = 0;
         sm.wn = 0;
         sm.cur = 0;
@@ -606,11 +635,16 @@ __global__ void __launch_bounds__(SQ_T) k_filter_out(FoArgs a) {
                 if (tid == 0) {
                     evals += sm.carry + ev;
                     sm.slot_out[j] = -1;
-                    if (c >= 0 && !(p.flags & PF_DAEMONSET)) fo_mark(a, c);
+                    if (!a.brk && c >= 0 && !(p.flags & PF_DAEMONSET)) fo_mark(a, c);
                     sm.j = j + 1;
+                    if (a.brk) sm.stop = 1;                     // breakOnFailure: the rows are written back
                 }
                 __threadfence();
                 __syncthreads();
+                if (a.brk) {
+                    sq_flush(a, sm);
+                    break;
+                }
                 if (c >= 0 && tid < sm.ns && sm.slot_cls[tid] == c)
                     sm.slot_mark[tid] = ld_mark(&a.cls_mark[CK(c, a.n_classes)]);
                 __syncthreads();
@@ -622,8 +656,14 @@ __global__ void __launch_bounds__(SQ_T) k_filter_out(FoArgs a) {
         sq_load_window(a, sm, sm.L);
         sq_load_slots(a, sm, false);
     }
+    if (sm.stop)                            // the pods behind the break: not run
+        for (int32_t k = sm.k0 + sm.ns + tid; k < a.P; k += SQ_T) {
+            a.out_node[k] = -1;
+            if (a.out_hok) a.out_hok[k] = 0;
+        }
     if (tid == 0) {
         if (sm.succ) a.ctl->L = sm.L;       // lastIndex moves only with a successful scan
+        a.ctl->tried = sm.stop ? sm.k0 + sm.j : a.P;
         a.ctl->evals = evals;
         a.ctl->phases = phases;
         a.ctl->seq_cycles = seq_cyc;
@@ -717,20 +757,26 @@ struct FbArgs {
     const uint8_t* cls_capped;
     const int32_t* cls_owner;
     FoCtl* ctl;
+    // TrySchedulePods (k_fb_walk<true>)
+    const uint64_t* acc0;                // [nwords] isNodeAcceptable bits (k_fb_acc); NULL: every node
+    uint8_t* out_hok;                    // per position: the hint passed CheckPredicates (NULL: not wanted)
+    int32_t brk;                         // breakOnFailure
 };
 
-// LDS layout of k_fb_walk, shared by the host sizing and the kernel
+// LDS layout of k_fb_walk, shared by the host sizing and the kernel.  svis: the words the
+// scans read, vis & acc; without a node mask they are the vis words themselves.
 struct FbLds {
-    size_t shapes, dyn, vis, stat, vpre, slot, bufrow, bufnode, dirty, ocnt, marks, oover, thr, total;
+    size_t shapes, dyn, vis, svis, stat, vpre, slot, bufrow, bufnode, dirty, ocnt, marks, oover, thr, total;
 };
 __host__ __device__ inline size_t fb_a16(size_t x) { return (x + 15) & ~(size_t)15; }
 __host__ __device__ inline FbLds fb_lds(int32_t S, int32_t NW, int32_t K, int32_t stat_in_lds, int32_t n_classes,
-                                        int32_t n_owners) {
+                                        int32_t n_owners, bool masked) {
     FbLds l;
     l.shapes = 0;
     l.dyn = l.shapes + sizeof(FbShape) * (size_t)(S > 0 ? S : 1);
     l.vis = l.dyn + sizeof(uint64_t) * (size_t)S * NW;
-    l.stat = l.vis + sizeof(uint64_t) * (size_t)NW;
+    l.svis = l.vis + (masked ? sizeof(uint64_t) * (size_t)NW : 0);
+    l.stat = l.svis + sizeof(uint64_t) * (size_t)NW;
     l.vpre = l.stat + (stat_in_lds ? sizeof(uint64_t) * (size_t)K * NW : 0);
     l.slot = l.vpre + fb_a16(sizeof(int32_t) * (size_t)(NW + 1));
     l.bufrow = l.slot + sizeof(int32_t) * FB_T;
@@ -781,6 +827,23 @@ __global__ void __launch_bounds__(256) k_fb_dyn(const NodeHot* __restrict__ hot,
         if (s < S) dyn[(size_t)s * nwords + w] = m;
         else vis[w] = m;
     }
+}
+
+// acc[w]: isNodeAcceptable as data (ca_match_spec: ALL / RANGE / MASK, minus `exclude`), one
+// bit per node.  Launched only when the match is not plain ALL.
+__global__ void __launch_bounds__(256) k_fb_acc(int32_t n, int32_t nwords, int32_t kind, int32_t lo, int32_t hi,
+                                               int32_t exclude, const uint8_t* __restrict__ mask,
+                                               uint64_t* __restrict__ acc) {
+    const int32_t node = (int32_t)(blockIdx.x * blockDim.x + threadIdx.x);
+    bool b = false;
+    if (node < n) {
+        b = node != exclude;
+        if (kind == CA_MATCH_RANGE) b = b && node >= lo && node < hi;
+        else if (kind == CA_MATCH_MASK) b = b && mask[node] != 0;
+    }
+    const uint64_t m = __ballot(b);
+    const int32_t w = node >> 6;
+    if ((threadIdx.x & 63) == 0 && w < nwords) acc[w] = m;
 }
 
 // static[c][w]: TaintToleration / NodeAffinity / NodeName of class c's representative pod
@@ -840,14 +903,27 @@ __device__ inline void fb_mark(const FbArgs& a, uint8_t* marks, int32_t* ocnt, u
     }
 }
 
+// GEN = false is FilterOutSchedulable's walk (ScheduleAnywhere, no break): svis is vis and the
+// break / hint_ok code is compiled out.  GEN = true is the general TrySchedulePods: the scans
+// read svis = vis & acc (the run fits, the mixed runs' fit masks, the first-set-bit searches
+// and the prefix counts behind the evaluation counts), the hint checks read the true vis
+// (a PF_TOL_UNSCHED pod passes CheckPredicates on an unschedulable node) and need the acc
+// bit to be accepted; a hint on a node outside acc is a hopeless hint (an unhinted pod plus
+// one evaluation) whose hint_ok is the predicate at batch load — exact, since no pod lands
+// outside acc during the call.  With the break, the first pod left without a node ends the
+// walk: the batch's rows are flushed, the pods behind it get -1 and `tried` goes to FoCtl.
+template <bool GEN>
 __global__ void __launch_bounds__(FB_T) k_fb_walk(FbArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char fb_smem[];
     const int lane = (int)threadIdx.x;
     const int32_t n = a.n, NW = a.nwords, S = a.S;
-    const FbLds lo = fb_lds(S, NW, a.K, a.stat_in_lds, a.n_classes, a.n_owners);
+    const bool masked = GEN && a.acc0 != nullptr;
+    const bool brk = GEN && a.brk != 0;
+    const FbLds lo = fb_lds(S, NW, a.K, a.stat_in_lds, a.n_classes, a.n_owners, masked);
     FbShape* shp = reinterpret_cast<FbShape*>(fb_smem + lo.shapes);
     uint64_t* dyn = reinterpret_cast<uint64_t*>(fb_smem + lo.dyn);                // [S][NW]
     uint64_t* vis = reinterpret_cast<uint64_t*>(fb_smem + lo.vis);                // [NW]
+    uint64_t* svis = reinterpret_cast<uint64_t*>(fb_smem + lo.svis);              // [NW] (vis itself unless masked)
     uint64_t* stat_l = reinterpret_cast<uint64_t*>(fb_smem + lo.stat);            // [K][NW] when in LDS
     int32_t* vpre = reinterpret_cast<int32_t*>(fb_smem + lo.vpre);                // [NW + 1]: visible nodes before word w
     int32_t* slot = reinterpret_cast<int32_t*>(fb_smem + lo.slot);                // a run's nodes
@@ -871,8 +947,11 @@ __global__ void __launch_bounds__(FB_T) k_fb_walk(FbArgs a) {
     for (int32_t base = 0; base < NW; base += FB_T) {
         const int32_t w = base + lane;
         const uint64_t v = w < NW ? a.vis0[w] : 0ull;
+        uint64_t sv = v;                                                        // what the scans see
+        if (masked) sv = w < NW ? v & a.acc0[w] : 0ull;
         if (w < NW) { vis[w] = v; dirty[w] = 0; }
-        const int32_t c = __builtin_popcountll(v);
+        if (masked && w < NW) svis[w] = sv;
+        const int32_t c = __builtin_popcountll(sv);
         const int32_t inc = wave_incl_scan(c);
         if (w < NW) vpre[w] = run_total + inc - c;
         run_total += __builtin_amdgcn_readlane(inc, 63);
@@ -887,9 +966,11 @@ __global__ void __launch_bounds__(FB_T) k_fb_walk(FbArgs a) {
     int32_t vpL = 0;                                                            // visible nodes before L
     {
         const int32_t w = L >> 6;
-        vpL = vpre[w] + __builtin_popcountll(vis[w] & bits_below(L & 63));
+        vpL = vpre[w] + __builtin_popcountll(svis[w] & bits_below(L & 63));
     }
     bool succ = false;
+    bool stopped = false;                                                       // breakOnFailure ended the walk
+    int32_t tried = a.P;
     unsigned long long evals = 0;
     int32_t overflowing = 0;
 #ifdef CASIM_PROF
@@ -966,12 +1047,17 @@ __global__ void __launch_bounds__(FB_T) k_fb_walk(FbArgs a) {
         // hint checks that can pass at all: the bits at the batch's start (placements only
         // clear bits, so a hint failing now fails later in the batch too)
         bool may = false;
+        bool hok_out = false;                                                   // hint_ok of a hint outside acc
         if (my_hinted) {
             const int32_t hw = lh >> 6;
             const uint64_t bit = 1ull << (lh & 63);
             const uint64_t hs = lp.scls >= 0 ? (stat_lds ? stat_l[(size_t)lp.scls * NW + hw]
                                                          : a.stat[(size_t)lp.scls * NW + hw]) : ~0ull;
             may = (dyn[(size_t)lp.shape * NW + hw] & hs & bit) && ((vis[hw] & bit) || (lp.flags & PF_TOL_UNSCHED));
+            if (masked && may && !(a.acc0[hw] & bit)) {                         // passes, not acceptable (:95, :102)
+                may = false;
+                hok_out = true;
+            }
         }
         const uint64_t may_mask = __ballot(may);
         // hinted pods whose hint fails for sure: one evaluation (CheckPredicates), then they
@@ -1025,7 +1111,7 @@ __global__ void __launch_bounds__(FB_T) k_fb_walk(FbArgs a) {
                     uint64_t fm = 0;                                             // bit k: node L + k fits my pod
                     if (un) {
                         const size_t dso = (size_t)lp.shape * NW;
-                        uint64_t g0 = dyn[dso + w0] & vis[w0], g1 = dyn[dso + w1] & vis[w1];
+                        uint64_t g0 = dyn[dso + w0] & svis[w0], g1 = dyn[dso + w1] & svis[w1];
                         if (lp.scls >= 0) {
                             g0 &= stat_lds ? stat_l[mso + w0] : a.stat[mso + w0];
                             g1 &= stat_lds ? stat_l[mso + w1] : a.stat[mso + w1];
@@ -1163,7 +1249,7 @@ __global__ void __launch_bounds__(FB_T) k_fb_walk(FbArgs a) {
                         if (sm) {
                             const int32_t xl = __builtin_amdgcn_readlane(x, 63 - __builtin_clzll(sm));
                             const int32_t lw = xl >> 6;
-                            const int32_t vpx = vpre[lw] + __builtin_popcountll(vis[lw] & bits_below(xl & 63)) + 1;
+                            const int32_t vpx = vpre[lw] + __builtin_popcountll(svis[lw] & bits_below(xl & 63)) + 1;
                             evals += (unsigned long long)(xl >= L ? vpx - vpL : vis_total - vpL + vpx);
                             L = xl + 1 == n ? 0 : xl + 1;                               // schedulerbased.go:131
                             vpL = L == 0 ? 0 : vpx;
@@ -1306,12 +1392,23 @@ __global__ void __launch_bounds__(FB_T) k_fb_walk(FbArgs a) {
             prof_fb[0] += pc1 - pc0;
 #endif
             const int32_t pre = first - j;                                      // pod j, already hint-checked
+            // breakOnFailure (hinting_simulator.go:83-85): pod j is left without a node in the
+            // three branches below; its own evaluations count, the pods behind it are not run
             if (sim >= 0 && marks[sim]) {                                       // similar pod known unschedulable
+                if (brk) {
+                    evals += hint_evals(first, 1 - pre);
+                    stopped = true;
+                    break;
+                }
                 evals += hint_evals(first, m - pre);
                 j += m;
                 continue;
             }
             if (pf & PF_PREFILTER_FAIL) {                                       // no node passes PreFilter (never hinted)
+                if (brk) {
+                    stopped = true;
+                    break;
+                }
                 if (sim >= 0 && !(pf & PF_DAEMONSET)) fb_mark(a, marks, ocnt, oover, sim, overflowing, lane);
                 j += (sim >= 0 && !(pf & PF_DAEMONSET) && marks[sim]) ? m : 1;
                 continue;
@@ -1327,7 +1424,7 @@ __global__ void __launch_bounds__(FB_T) k_fb_walk(FbArgs a) {
                 if (w >= NW) w -= NW;
                 uint64_t mask = r == 0 ? bits_from(b0) : (r == NW ? bits_below(b0) : ~0ull);
                 if (r > last) mask = 0;
-                uint64_t f = ds[w] & vis[w] & mask;
+                uint64_t f = ds[w] & svis[w] & mask;
                 if (c >= 0) f &= stat_lds ? stat_l[so + w] : a.stat[so + w];
                 const int32_t cf = __builtin_popcountll(f);
                 const int32_t inc = wave_incl_scan(cf);
@@ -1345,6 +1442,11 @@ __global__ void __launch_bounds__(FB_T) k_fb_walk(FbArgs a) {
             prof_fb[1] += pc2 - pc1;
 #endif
             if (k == 0) {                                                       // no node fits: every run pod fails
+                if (brk) {                                                      // pod j scanned the whole ring
+                    evals += (unsigned long long)vis_total + hint_evals(first, 1 - pre);
+                    stopped = true;
+                    break;
+                }
                 const bool can_mark = sim >= 0 && !(pf & PF_DAEMONSET);
                 if (can_mark) fb_mark(a, marks, ocnt, oover, sim, overflowing, lane);
                 // a marked class skips the rest of the run; otherwise (no class, DaemonSet, a
@@ -1357,7 +1459,7 @@ __global__ void __launch_bounds__(FB_T) k_fb_walk(FbArgs a) {
             // the visible nodes from L to the last fit (inclusive) were evaluated
             const int32_t xl = slot[k - 1];
             const int32_t xw = xl >> 6;
-            const int32_t vpx = vpre[xw] + __builtin_popcountll(vis[xw] & bits_below(xl & 63)) + 1;
+            const int32_t vpx = vpre[xw] + __builtin_popcountll(svis[xw] & bits_below(xl & 63)) + 1;
             evals += (unsigned long long)(xl >= L ? vpx - vpL : vis_total - vpL + vpx);
             place(k, s, false, NodeHot{});
             evals += hint_evals(first, k - pre);
@@ -1374,11 +1476,26 @@ __global__ void __launch_bounds__(FB_T) k_fb_walk(FbArgs a) {
         if (lane < cnt) {
             a.out_node[base + lane] = out;
             if (out >= 0) a.hints[base + lane] = out;                           // Hints.Set (:95, :123)
+            if (GEN && a.out_hok) {
+                // a hinted pod sits on its hinted node only through the hint check (a scan never
+                // picks a node whose check failed: the bits only clear); lanes behind a break: 0
+                const bool ran = !stopped || lane <= j;
+                a.out_hok[base + lane] = ran && ((my_hinted && out == lh) || hok_out) ? 1 : 0;
+            }
+        }
+        if (GEN && stopped) {
+            tried = base + j + 1;
+            for (int32_t k = base + FB_T + lane; k < a.P; k += FB_T) {         // the batches behind the break
+                a.out_node[k] = -1;
+                if (a.out_hok) a.out_hok[k] = 0;
+            }
+            break;
         }
     }
     for (int32_t i = lane; i < a.n_classes; i += FB_T) a.cls_mark[i] = marks[i];
     if (lane == 0) {
         if (succ) a.ctl->L = L;
+        a.ctl->tried = tried;
         a.ctl->evals = evals;
         a.ctl->overflowing = overflowing;
         a.ctl->phases = (a.P + FB_T - 1) / FB_T;
@@ -1399,14 +1516,18 @@ __global__ void __launch_bounds__(FB_T) k_fb_walk(FbArgs a) {
 
 using namespace casim;
 
-extern "C" {
-
-int ca_filter_out_schedulable(ca_mirror* m, const ca_pod_table* t, const ca_podset* s, const int32_t* order,
-                              int32_t n, const int32_t* class_owner, int32_t n_classes, int32_t* hints,
-                              int32_t* last_index, int32_t* out_node, int32_t* out_pod_id, int32_t* n_overflowing,
-                              uint64_t* evals, int32_t* n_placed) {
+// HintingSimulator.TrySchedulePods (hinting_simulator.go:58-125) in one device call: the core
+// of ca_try_schedule_pods and of ca_filter_out_schedulable (match NULL, no break, no hint_ok:
+// the launches and copies of that leg are the ones it always made).
+static int try_schedule_core(ca_mirror* m, const ca_pod_table* t, const ca_podset* s, const int32_t* order,
+                             int32_t n, const ca_match_spec* match, int32_t break_on_failure,
+                             const int32_t* class_owner, int32_t n_classes, int32_t* hints, int32_t* last_index,
+                             int32_t* out_node, int32_t* out_pod_id, uint8_t* out_hint_ok, int32_t* n_overflowing,
+                             uint64_t* evals, int32_t* n_placed, int32_t* n_tried) {
     if (!m || !t || n < 0 || n_classes < 0 || !last_index || (n > 0 && !out_node)) return CA_EINVAL;
     if (s && (s->m != m || s->t.n_pods != t->n_pods)) return CA_EINVAL;
+    const int32_t mkind = match ? match->kind : CA_MATCH_ALL;
+    if (mkind == CA_MATCH_MASK && !match->mask) return CA_EINVAL;          // ca_fits_any_node's rule
     const auto t0 = std::chrono::steady_clock::now();
     const bool dbg_t = knob_env("CASIM_DEBUG_TIMING") != nullptr;
     auto tmark = [&](const char* what) {
@@ -1427,6 +1548,7 @@ int ca_filter_out_schedulable(ca_mirror* m, const ca_pod_table* t, const ca_pods
     if (m->n_scope_blockers > 0 || oos) return CA_EUNSUPPORTED;
     if (n_overflowing) *n_overflowing = 0;
     if (n_placed) *n_placed = 0;
+    if (n_tried) *n_tried = 0;
     FilterScratch& fo = m->fo;
     fo.kernel_ms = 0;
     fo.phases = fo.steps = fo.ring_scans = fo.windows = 0;
@@ -1458,13 +1580,23 @@ int ca_filter_out_schedulable(ca_mirror* m, const ca_pod_table* t, const ca_pods
             capped[c] = class_owner[c] >= 0 && per_owner[class_owner[c]] > FO_MAX_PER_OWNER;
     }
     const int32_t nn = (int32_t)m->nodes.size();
-    // inputs: order | hints | class_owner | capped ; zeroed: ctl | owner_cnt | cls_mark | owner_over
+    const int32_t NW = (nn + 63) / 64;
+    // isNodeAcceptable: plain ALL (no kind, no node to exclude) builds no acc words
+    const int32_t mexcl = match ? match->exclude : -1;
+    const bool ranged = mkind == CA_MATCH_RANGE, bymask = mkind == CA_MATCH_MASK;
+    const bool masked = nn > 0 && (ranged || bymask || (mexcl >= 0 && mexcl < nn));
+    const bool general = masked || break_on_failure != 0 || out_hint_ok != nullptr;
+    // inputs: order | hints | class_owner | capped | node mask bytes ; zeroed: ctl | owner_cnt | cls_mark | owner_over
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const size_t o_order = 0, o_hints = o_order + al(sizeof(int32_t) * n), o_owner = o_hints + al(sizeof(int32_t) * n),
-                 o_capped = o_owner + al(sizeof(int32_t) * (n_classes + 1)), in_bytes = o_capped + al(n_classes + 1);
+                 o_capped = o_owner + al(sizeof(int32_t) * (n_classes + 1)), o_mask = o_capped + al(n_classes + 1),
+                 in_bytes = o_mask + (masked && bymask ? al((size_t)nn) : 0);
     const size_t z_ctl = 0, z_ocnt = al(sizeof(FoCtl)), z_mark = z_ocnt + al(sizeof(int32_t) * (n_owners + 1)),
                  z_over = z_mark + al(n_classes + 1), z_bytes = z_over + al(n_owners + 1);
-    const size_t out_bytes = al(sizeof(int32_t) * n) * 2 + al(sizeof(FoCtl));
+    // outputs: out_node | hints | ctl | hint_ok (when asked for)
+    const size_t o_hok = al(sizeof(int32_t) * n) * 2 + al(sizeof(FoCtl));
+    const size_t out_bytes = o_hok + (out_hint_ok ? al((size_t)n) : 0);
+    if (masked && (rc = fo.acc.reserve(sizeof(uint64_t) * (size_t)NW)) != CA_OK) return rc;
     if ((rc = fo.in.reserve(in_bytes)) != CA_OK || (rc = fo.h_in.reserve(in_bytes)) != CA_OK ||
         (rc = fo.zero.reserve(z_bytes)) != CA_OK || (rc = fo.out.reserve(out_bytes)) != CA_OK ||
         (rc = fo.h_out.reserve(out_bytes)) != CA_OK)
@@ -1479,6 +1611,7 @@ int ca_filter_out_schedulable(ca_mirror* m, const ca_pod_table* t, const ca_pods
     tmark("inputs");
     if (class_owner) std::memcpy(hi + o_owner, class_owner, sizeof(int32_t) * n_classes);
     std::memcpy(hi + o_capped, capped.data(), (size_t)n_classes);
+    if (masked && bymask) std::memcpy(hi + o_mask, match->mask, (size_t)nn);
     FoCtl ctl0;
     std::memset(&ctl0, 0, sizeof ctl0);
     ctl0.L = *last_index;
@@ -1516,6 +1649,9 @@ int ca_filter_out_schedulable(ca_mirror* m, const ca_pod_table* t, const ca_pods
     a.n_pods = dp->n_pods;
     a.n_classes = n_classes;
     a.n_owners = n_owners;
+    a.acc = masked ? fo.acc.as<const uint64_t>() : nullptr;
+    a.out_hok = out_hint_ok ? reinterpret_cast<uint8_t*>(dout + o_hok) : nullptr;
+    a.brk = break_on_failure != 0;
     // Feasibility-bitmap walk when every pending pod qualifies (no host ports, no scalar
     // requests, no PreFilter NodeNames; <= 64 resource shapes; the bitmaps fit LDS); the
     // window sequencer otherwise (CASIM_FO_WINDOW forces it, for tests of both).
@@ -1526,7 +1662,6 @@ int ca_filter_out_schedulable(ca_mirror* m, const ca_pod_table* t, const ca_pods
     std::vector<int32_t> fb_rep;
     int32_t fb_stat_in_lds = 0;
     bool fb = nn > 0 && !knob_env("CASIM_FO_WINDOW");
-    const int32_t NW = (nn + 63) / 64;
     if (fb) {
         // one pass over the node rows (host workers): the taints any node has, and the largest
         // free cpu / memory / ephemeral of any node with a free pod slot (the dead-shape test below)
@@ -1705,11 +1840,17 @@ int ca_filter_out_schedulable(ca_mirror* m, const ca_pod_table* t, const ca_pods
         // LDS: shapes, bitmaps, vis prefix counts, run scratch and the similar-pods state,
         // plus the static words when they fit too
         const int32_t S = (int32_t)fb_shapes.size(), K = (int32_t)fb_rep.size();
-        fb_stat_in_lds = K > 0 && fb_lds(S, NW, K, 1, n_classes, n_owners).total <= FB_LDS_MAX ? 1 : 0;
-        if (fb_lds(S, NW, K, fb_stat_in_lds, n_classes, n_owners).total > FB_LDS_MAX) fb = false;
+        fb_stat_in_lds = K > 0 && fb_lds(S, NW, K, 1, n_classes, n_owners, masked).total <= FB_LDS_MAX ? 1 : 0;
+        if (fb_lds(S, NW, K, fb_stat_in_lds, n_classes, n_owners, masked).total > FB_LDS_MAX) fb = false;
     }
     tmark("prepared");
     CA_HIP_CHECK(hipEventRecord(m->ev0, m->stream));
+    if (masked) {                                      // both kernels read the same acc words
+        hipLaunchKernelGGL(k_fb_acc, dim3((nn + 255) / 256), dim3(256), 0, m->stream, nn, NW, mkind,
+                           match ? match->lo : 0, match ? match->hi : 0, mexcl,
+                           bymask ? reinterpret_cast<const uint8_t*>(di + o_mask) : nullptr, fo.acc.as<uint64_t>());
+        CA_HIP_CHECK(hipGetLastError());
+    }
     if (fb) {
         const int32_t S = (int32_t)fb_shapes.size(), K = (int32_t)fb_rep.size();
         const size_t b_pods = al(sizeof(FbPod) * n), b_sh = al(sizeof(FbShape) * std::max(S, 1)),
@@ -1770,9 +1911,15 @@ int ca_filter_out_schedulable(ca_mirror* m, const ca_pod_table* t, const ca_pods
         fa.hints = a.hints; fa.out_node = a.out_node;
         fa.cls_mark = a.cls_mark; fa.cls_capped = a.cls_capped; fa.cls_owner = a.cls_owner;
         fa.ctl = a.ctl;
-        const size_t lds_all = fb_lds(S, NW, K, fb_stat_in_lds, n_classes, n_owners).total;
-        if ((rc = ensure_dyn_lds((const void*)k_fb_walk, lds_all)) != CA_OK) return rc;
-        hipLaunchKernelGGL(k_fb_walk, dim3(1), dim3(FB_T), lds_all, m->stream, fa);
+        fa.acc0 = a.acc; fa.out_hok = a.out_hok; fa.brk = a.brk;
+        const size_t lds_all = fb_lds(S, NW, K, fb_stat_in_lds, n_classes, n_owners, masked).total;
+        if (general) {
+            if ((rc = ensure_dyn_lds((const void*)k_fb_walk<true>, lds_all)) != CA_OK) return rc;
+            hipLaunchKernelGGL(k_fb_walk<true>, dim3(1), dim3(FB_T), lds_all, m->stream, fa);
+        } else {
+            if ((rc = ensure_dyn_lds((const void*)k_fb_walk<false>, lds_all)) != CA_OK) return rc;
+            hipLaunchKernelGGL(k_fb_walk<false>, dim3(1), dim3(FB_T), lds_all, m->stream, fa);
+        }
         CA_HIP_CHECK(hipGetLastError());
         fo.path = 1;
         fo.fb_shapes = S;
@@ -1788,6 +1935,9 @@ int ca_filter_out_schedulable(ca_mirror* m, const ca_pod_table* t, const ca_pods
                                 m->stream));
     FoCtl* hctl = reinterpret_cast<FoCtl*>(ho + al(sizeof(int32_t) * n) * 2);
     CA_HIP_CHECK(hipMemcpyAsync(hctl, a.ctl, sizeof(FoCtl), hipMemcpyDeviceToHost, m->stream));
+    if (out_hint_ok) {
+        CA_HIP_CHECK(hipMemcpyAsync(ho + o_hok, dout + o_hok, (size_t)n, hipMemcpyDeviceToHost, m->stream));
+    }
     CA_HIP_CHECK(hipStreamSynchronize(m->stream));
     CA_HIP_CHECK(hipEventElapsedTime(&fo.kernel_ms, m->ev0, m->ev1));
     if (hctl->bad_line) {
@@ -1805,6 +1955,8 @@ int ca_filter_out_schedulable(ca_mirror* m, const ca_pod_table* t, const ca_pods
         if (hints) hints[k] = hints_out[k];
         placed += nodes_out[k] >= 0;
     }
+    if (out_hint_ok) std::memcpy(out_hint_ok, ho + o_hok, (size_t)n);
+    if (n_tried) *n_tried = hctl->tried;
     const size_t pods0 = m->pods.size(), terms0 = m->terms.size(), reqs0 = m->reqs.size(), names0 = m->pf_names.size();
     const bool dev_in_sync = m->d_pods_synced == pods0 && (size_t)m->d_pods.n_pods == pods0 && m->d_terms_synced == terms0 &&
                              (size_t)m->d_pods.n_reqs == reqs0 && (size_t)m->d_pods.n_names == names0;
@@ -1834,6 +1986,26 @@ int ca_filter_out_schedulable(ca_mirror* m, const ca_pod_table* t, const ca_pods
     fo.total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     if (n_placed) *n_placed = placed;
     return CA_OK;
+}
+
+extern "C" {
+
+int ca_filter_out_schedulable(ca_mirror* m, const ca_pod_table* t, const ca_podset* s, const int32_t* order,
+                              int32_t n, const int32_t* class_owner, int32_t n_classes, int32_t* hints,
+                              int32_t* last_index, int32_t* out_node, int32_t* out_pod_id, int32_t* n_overflowing,
+                              uint64_t* evals, int32_t* n_placed) {
+    // ScheduleAnywhere, breakOnFailure=false (filter_out_schedulable.go:105)
+    return try_schedule_core(m, t, s, order, n, nullptr, 0, class_owner, n_classes, hints, last_index, out_node,
+                             out_pod_id, nullptr, n_overflowing, evals, n_placed, nullptr);
+}
+
+int ca_try_schedule_pods(ca_mirror* m, const ca_pod_table* t, const ca_podset* s, const int32_t* order, int32_t n,
+                         const ca_match_spec* match, int32_t break_on_failure, const int32_t* class_owner,
+                         int32_t n_classes, int32_t* hints, int32_t* last_index, int32_t* out_node,
+                         int32_t* out_pod_id, uint8_t* out_hint_ok, int32_t* n_overflowing, uint64_t* evals,
+                         int32_t* n_placed, int32_t* n_tried) {
+    return try_schedule_core(m, t, s, order, n, match, break_on_failure, class_owner, n_classes, hints, last_index,
+                             out_node, out_pod_id, out_hint_ok, n_overflowing, evals, n_placed, n_tried);
 }
 
 int ca_filter_stats(const ca_mirror* m, float* out, int32_t cap) {

@@ -84,9 +84,10 @@ struct SweepScratch {
     }
 };
 
-// Per-mirror scratch of ca_filter_out_schedulable (filter.hip).
+// Per-mirror scratch of ca_filter_out_schedulable / ca_try_schedule_pods (filter.hip).
 struct FilterScratch {
     DevBuf in, zero, out;          // inputs (order, hints, class tables), zeroed state, outputs
+    DevBuf acc;                    // ca_try_schedule_pods: isNodeAcceptable, one bit per node
     HostBuf h_in, h_out;
     DevPodTable pods;              // the pending table when the caller passes no podset
     HostBuf h_pods;                // ... staged in page-locked memory (its copies run beside the preparation)

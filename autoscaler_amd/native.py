@@ -102,6 +102,8 @@ def load() -> C.CDLL:
         "ca_removal_timings": ([vp, p(C.c_float), i32], C.c_int),
         "ca_filter_out_schedulable": ([vp, vp, vp, vp, i32, vp, i32, vp, p(i32), vp, vp, p(i32), p(C.c_uint64), p(i32)],
                                       C.c_int),
+        "ca_try_schedule_pods": ([vp, vp, vp, vp, i32, vp, i32, vp, i32, vp, p(i32), vp, vp, vp, p(i32),
+                                  p(C.c_uint64), p(i32), p(i32)], C.c_int),
         "ca_filter_stats": ([vp, p(C.c_float), i32], C.c_int),
         "ca_util_table_create": ([i32, vp, i32, vp, vp, p(vp)], C.c_int),
         "ca_util_table_destroy": ([vp], C.c_int),
@@ -189,7 +191,7 @@ def exported_symbols() -> list[str]:
         "ca_removal_stats", "ca_removal_timings", "ca_removal_plan_create", "ca_removal_plan_run",
         "ca_removal_plan_destroy", "ca_removal_plan_sensitive_pods", "ca_removal_plan_phased",
         "ca_removal_plan_run_phase", "ca_sweep_compose", "ca_mirror_set_hints", "ca_mirror_get_hints",
-        "ca_removal_candidate_ticks", "ca_filter_out_schedulable", "ca_filter_stats",
+        "ca_removal_candidate_ticks", "ca_filter_out_schedulable", "ca_try_schedule_pods", "ca_filter_stats",
         "ca_util_table_create", "ca_util_table_destroy", "ca_util_calculate", "ca_util_device_results",
         "ca_util_table_update", "ca_util_table_set_added", "ca_multi_create", "ca_multi_destroy",
         "ca_multi_estimate_plan_create", "ca_multi_estimate_plan_run",
@@ -312,6 +314,13 @@ class FilterOutput:
 
 
 @dataclass
+class TryScheduleOutput(FilterOutput):
+    """ca_try_schedule_pods: FilterOutput plus the break position and the hint checks."""
+    tried: int = 0               # pods processed (the one the break stopped at included)
+    hint_ok: np.ndarray = None   # uint8 [n]: the pod's hint passed CheckPredicates (Hints.Set, :95)
+
+
+@dataclass
 class _FilterArgs:
     order: np.ndarray
     n: int
@@ -354,6 +363,7 @@ class Mirror:
     """A ``ca_mirror``: the HBM-resident ClusterSnapshot data plane."""
 
     backend_name = "native"
+    batched_try_schedule = True      # try_schedule_pods(table, ...): HintingSimulator's one-call path
 
     def __init__(self, device: int = 0):
         self.lib = load()
@@ -509,6 +519,29 @@ class Mirror:
                                                   C.byref(li), ptr(a.node), ptr(a.pod_id), C.byref(ov),
                                                   C.byref(ev), C.byref(placed)), "ca_filter_out_schedulable")
         return a.output(placed.value, li.value, ev.value, ov.value)
+
+    def try_schedule_pods(self, table: abi.PodTable, order=None, match=None, break_on_failure: bool = False,
+                          class_owner=None, hints=None, last_index: int = 0, podset=None) -> TryScheduleOutput:
+        """ca_try_schedule_pods: HintingSimulator.TrySchedulePods(pods, isNodeAcceptable,
+        breakOnFailure) in one device call (hinting_simulator.go:58-125).  `match`: the
+        (kind, lo, hi, exclude, mask) tuple of fits_any_node, None for every node."""
+        a = filter_args(table, order, class_owner, hints)
+        ms, mask = abi.match_spec(*(match or ()))
+        li = C.c_int32(last_index)
+        ev = C.c_uint64(0)
+        ov = C.c_int32(0)
+        placed = C.c_int32(0)
+        tried = C.c_int32(0)
+        hok = np.zeros(max(a.n, 1), np.uint8)
+        _check(self.lib.ca_try_schedule_pods(self.h, table.ref, podset.h if podset is not None else None,
+                                             ptr(a.order), a.n, C.byref(ms) if match is not None else None,
+                                             int(bool(break_on_failure)), a.owner_ptr, a.n_classes, ptr(a.hints),
+                                             C.byref(li), ptr(a.node), ptr(a.pod_id), ptr(hok), C.byref(ov),
+                                             C.byref(ev), C.byref(placed), C.byref(tried)), "ca_try_schedule_pods")
+        del mask
+        o = a.output(placed.value, li.value, ev.value, ov.value)
+        return TryScheduleOutput(o.node, o.pod_id, o.hints, o.placed, o.last_index, o.evals, o.n_overflowing,
+                                 tried.value, hok[: a.n])
 
     def filter_stats(self) -> dict:
         out = (C.c_float * 16)()

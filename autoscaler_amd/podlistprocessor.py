@@ -10,13 +10,11 @@ spec, similar_pods.go:43-111) as class ids with their controllers.
 """
 from __future__ import annotations
 
-import numpy as np
-
 from .clustersnapshot import ClusterSnapshot
 from .gosort import sort_slice_desc
 from .k8s import Pod
 from .predicatechecker import SchedulerBasedPredicateChecker, unsupported
-from .simulator import HintingSimulator, Hints, Status
+from .simulator import HintingSimulator, Hints, Status, pending_call_inputs
 
 
 def PodPriority(pod: Pod) -> int:  # noqa: N802 - corev1helpers.PodPriority
@@ -28,18 +26,10 @@ def TrySchedulePodsAnywhere(sim: HintingSimulator, snapshot: ClusterSnapshot, po
     (hinting_simulator.go:58-89) as one batched call; returns (statuses, overflowing)."""
     if not pods:
         return [], 0
-    table = snapshot.encode(pods)
-    n_classes = int(table.pods["similar_class"].max()) + 1
-    owners = snapshot.interner.class_owners(max(n_classes, 0))
-    hints = np.full(len(pods), -1, np.int32)
-    for k, pod in enumerate(pods):
-        name, ok = sim.hints.Get(Hints.key(pod))
-        if ok and name in snapshot._state.pos:
-            hints[k] = snapshot.position(name)
+    table, owners, hints = pending_call_inputs(sim.hints, snapshot, pods)
     pc = sim.predicate_checker
     with unsupported("FilterOutSchedulable: a pending pod or the snapshot is out of kernel scope"):
-        out = snapshot.backend.filter_out_schedulable(table, None, owners if n_classes > 0 else None, hints,
-                                                      pc.last_index)
+        out = snapshot.backend.filter_out_schedulable(table, None, owners, hints, pc.last_index)
     pc.last_index = out.last_index
     pc.evals += int(out.evals)
     statuses, placed = [], []

@@ -118,9 +118,26 @@ class SimilarPodsScheduling:
         lst.append(self._sig(pod))
 
 
+def pending_call_inputs(hints: Hints, snapshot: ClusterSnapshot, pods: list):
+    """What a batched TrySchedulePods call needs of its pods: the interned table (with the
+    similar-pods classes, similar_pods.go:43-111), the classes' controllers (None without
+    classes) and Hints.Get per pod as node positions (-1: no hint, or a node that is gone)."""
+    table = snapshot.encode(pods)
+    n_classes = int(table.pods["similar_class"].max()) + 1
+    owners = snapshot.interner.class_owners(n_classes) if n_classes > 0 else None
+    pos = np.full(len(pods), -1, np.int32)
+    for k, pod in enumerate(pods):
+        name, ok = hints.Get(Hints.key(pod))
+        if ok and name in snapshot._state.pos:
+            pos[k] = snapshot.position(name)
+    return table, owners, pos
+
+
 class HintingSimulator:
-    """scheduling.HintingSimulator (hinting_simulator.go:36-135) composed from the
-    predicate-checker entry points (one device call per pod: the compatibility path)."""
+    """scheduling.HintingSimulator (hinting_simulator.go:36-135).  TrySchedulePods is one
+    device call for the whole list (ca_try_schedule_pods); TrySchedulePodsPerPod composes it
+    from the predicate-checker entry points, one device call per pod: the slow path, kept as
+    the independent comparison."""
 
     def __init__(self, predicate_checker: SchedulerBasedPredicateChecker):
         self.predicate_checker = predicate_checker
@@ -128,6 +145,40 @@ class HintingSimulator:
 
     def TrySchedulePods(self, snapshot: ClusterSnapshot, pods: list, is_node_acceptable=None,  # noqa: N802
                         break_on_failure: bool = False):
+        """hinting_simulator.go:58-89.  is_node_acceptable (None, a callable on NodeInfo or a
+        set of node names) is evaluated once per node, on the snapshot as the call finds it."""
+        if not getattr(snapshot.backend, "batched_try_schedule", False):
+            # a backend with the three primitives only (the CPU restatement the tests check against)
+            return self.TrySchedulePodsPerPod(snapshot, pods, is_node_acceptable, break_on_failure)
+        if not pods:
+            return [], 0, None
+        pc = self.predicate_checker
+        table, owners, hints = pending_call_inputs(self.hints, snapshot, pods)
+        match = None if is_node_acceptable is None else pc._match(snapshot, is_node_acceptable)
+        with unsupported("TrySchedulePods: a pod or the snapshot is out of kernel scope"):
+            out = snapshot.backend.try_schedule_pods(table, None, match, break_on_failure, owners, hints,
+                                                     pc.last_index)
+        pc.last_index = out.last_index
+        pc.evals += int(out.evals)
+        statuses, placed = [], []
+        for k, pod in enumerate(pods[: out.tried]):
+            hk = Hints.key(pod)
+            if out.hint_ok[k]:                                         # :95, before isNodeAcceptable
+                self.hints.Set(hk, snapshot.name_at(int(hints[k])))
+            node = int(out.node[k])
+            if node < 0:
+                continue
+            name = snapshot.name_at(node)
+            self.hints.Set(hk, name)                                   # :123 (a re-set when hinted)
+            statuses.append(Status(pod, name))
+            placed.append((pod, name, int(out.pod_id[k])))
+        snapshot.record_added_pods(placed)
+        return statuses, int(out.n_overflowing), None
+
+    def TrySchedulePodsPerPod(self, snapshot: ClusterSnapshot, pods: list, is_node_acceptable=None,  # noqa: N802
+                              break_on_failure: bool = False):
+        """The reference loop over CheckPredicates / FitsAnyNodeMatching / AddPod: two device
+        calls per pod."""
         similar = SimilarPodsScheduling()
         statuses = []
         pc = self.predicate_checker

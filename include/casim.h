@@ -523,6 +523,38 @@ int ca_filter_out_schedulable(ca_mirror* m, const ca_pod_table* t, const ca_pods
                               int32_t n_classes, int32_t* hints, int32_t* last_index,
                               int32_t* out_node, int32_t* out_pod_id, int32_t* n_overflowing,
                               uint64_t* evals, int32_t* n_placed);
+/* HintingSimulator.TrySchedulePods(snapshot, pods, isNodeAcceptable, breakOnFailure)
+ * (CA/simulator/scheduling/hinting_simulator.go:58-125), the general form of the call above:
+ * one device call for the whole list.  order, s, class_owner / n_classes, hints, last_index,
+ * out_node, out_pod_id, n_overflowing, evals and n_placed are ca_filter_out_schedulable's,
+ * and so are the placements on the current fork level, the CA_EINVAL checks and the
+ * CA_EUNSUPPORTED scope rule (nothing runs).  ca_filter_out_schedulable is this call with
+ * match NULL and break_on_failure 0.
+ *  match        isNodeAcceptable as data, validated as ca_fits_any_node validates it (NULL:
+ *               CA_MATCH_ALL; CA_MATCH_MASK needs a mask of node-count bytes); `exclude`
+ *               applies to every kind.  A scan skips a node the match rejects without
+ *               counting an evaluation (schedulerbased.go:116), like an Unschedulable node;
+ *               the node keeps its place in the ring, so lastIndex counts all nodes.
+ *  hints        CheckPredicates on the hinted node ignores `match` and costs one evaluation
+ *               (none for a CA_POD_PREFILTER_FAIL pod).  If it passes and the node matches,
+ *               the pod goes there (:102); if it passes and the node does not match, the pod
+ *               falls through to the scan.
+ *  out_hint_ok[k]  (may be NULL) 1 exactly when pod k had a hint and that CheckPredicates
+ *               passed, accepted or not: the reference's Hints.Set at :95 comes before
+ *               isNodeAcceptable, so a caller that keeps hint generations sets from this.
+ *  break_on_failure != 0: the walk ends at the first pod left without a node (:83-85), a pod
+ *               skipped by the similar-pods cache included.  *n_tried (may be NULL) is the
+ *               number of pods processed, the failing one included; its evaluations count.
+ *               Pods k >= *n_tried get out_node = out_pod_id = -1 and out_hint_ok = 0, keep
+ *               their hints[k] and add no evaluations.  Without the break *n_tried == n. */
+int ca_try_schedule_pods(ca_mirror* m, const ca_pod_table* t, const ca_podset* s,
+                         const int32_t* order, int32_t n,
+                         const ca_match_spec* match, int32_t break_on_failure,
+                         const int32_t* class_owner, int32_t n_classes,
+                         int32_t* hints, int32_t* last_index,
+                         int32_t* out_node, int32_t* out_pod_id, uint8_t* out_hint_ok,
+                         int32_t* n_overflowing, uint64_t* evals,
+                         int32_t* n_placed, int32_t* n_tried);
 /* [0] device time of the last call's kernels, [1] host wall time of the call (ms),
  * [2] slot phases, [3] block steps, [4] block-wide ring scans, [5] window loads, [6] share of the
  * kernel's cycles in wave 0's walk and [7] walk cycles per pod (both CASIM_PROF builds only, else 0),
