@@ -16,6 +16,8 @@ CASIM_ABI_VERSION = 3
 # status codes
 CA_OK, CA_EINVAL, CA_ENOTFOUND, CA_EEXISTS, CA_EDEVICE, CA_ECAPACITY, CA_EUNSUPPORTED, CA_ESTATE, CA_ENOTRUN = range(9)
 
+CA_EXPANDER_MOST_PODS, CA_EXPANDER_LEAST_WASTE = 1, 2     # ca_expander_best_options filters
+
 CA_MAX_SCALAR = 8
 CA_LABEL_WORDS = 4
 CA_PORT_WORDS = 2

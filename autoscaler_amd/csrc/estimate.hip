@@ -2602,6 +2602,12 @@ struct ca_estimate_plan {
     int32_t map_max_nodes = -1, n_heavy = 0;
     int32_t map_source = 0;        // 1: demand model, 2: the chains' measured times (previous run)
     int32_t res_device = -1;       // the streams and events below came from the pool of this device
+    // the last run left its final pod ids in d_sched_pod (not stream positions or the parts
+    // a zero-copy publisher did not need), and every group's n_scheduled: what the readers
+    // of the resident lists (expander.hip) go by
+    bool lists_final = false;
+    std::vector<int32_t> last_nsched;
+    mutable OptionSumsScratch opt_scratch;
     ~ca_estimate_plan();
 };
 
@@ -3192,6 +3198,7 @@ int plan_run(ca_estimate_plan* p, const ca_limiter* lim, int32_t* last_index, ca
     // 16-bit results: pod ids of a podset of at most 65535 pods (0xFFFF: not scheduled)
     if (sched16 && (sched_pod || sched_node || p->s->n_host > 65535)) return CA_EINVAL;
     p->pub_state = 0;
+    p->lists_final = false;
     const auto t_start = std::chrono::steady_clock::now();
     // CASIM_STEP_TIMING (read once per process): host-side split of the steps, averaged over
     // 20 calls — entry to the first launch, to the last launch, to the join, to the return,
@@ -3862,6 +3869,11 @@ int plan_run(ca_estimate_plan* p, const ca_limiter* lim, int32_t* last_index, ca
             st_n = 0;
         }
     }
+    p->last_nsched.resize((size_t)G);
+    for (int32_t g = 0; g < G; g++) p->last_nsched[g] = results[g].status == CA_OK ? results[g].n_scheduled : 0;
+    // (a publisher that ran to its end wrote the caller's buffer only: d_sched_pod then holds
+    // stream positions or single placements alone)
+    p->lists_final = !publish || p->pub_state == 2;
     return CA_OK;
 }
 
@@ -3880,6 +3892,20 @@ int32_t estimate_plan_rebase(const ca_estimate_plan* p, ca_estimate_result* resu
         else r.last_index_out = cur;
     }
     return cur;
+}
+}  // namespace casim
+
+namespace casim {
+void estimate_plan_lists(const ca_estimate_plan* p, PlanLists* out) {
+    out->m = p->m;
+    out->s = p->s;
+    out->G = p->G;
+    out->total = p->total;
+    out->h_off = p->h_off.data();
+    out->h_nsched = p->last_nsched.data();
+    out->d_sched_pod = p->d_sched_pod.as<int32_t>();
+    out->final_lists = p->lists_final && (int32_t)p->last_nsched.size() == p->G;
+    out->scratch = &p->opt_scratch;
 }
 }  // namespace casim
 

@@ -337,3 +337,31 @@ struct ca_podset {
     // template (checked per plan: ca_estimate_plan::decouple_ok)
     bool cls_uniform = false;
 };
+
+namespace casim {
+// Buffers and events of ca_estimate_plan_option_sums (expander.hip), kept in the plan so a
+// caller that picks an option every loop allocates them once.
+struct OptionSumsScratch {
+    DevBuf d_in, d_sums;            // [off | n_scheduled | tile prefix] of the groups; G x 2 sums + 1
+    HostBuf h;                      // page-locked staging of both
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    bool timed = false;             // ev0 / ev1 bracket a kernel of the last call
+    ~OptionSumsScratch() {
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+    }
+};
+
+// What expander.hip reads of an Estimate plan (the struct itself is private to estimate.hip).
+struct PlanLists {
+    ca_mirror* m = nullptr;
+    const ca_podset* s = nullptr;
+    int32_t G = 0, total = 0;
+    const int32_t* h_off = nullptr;        // [G + 1] group offsets into the lists
+    const int32_t* h_nsched = nullptr;     // [G] n_scheduled of the last run (0 for a group not CA_OK)
+    const int32_t* d_sched_pod = nullptr;  // the device lists, sched_pod layout
+    bool final_lists = false;              // the last run left its final ids in d_sched_pod
+    OptionSumsScratch* scratch = nullptr;
+};
+void estimate_plan_lists(const ca_estimate_plan* p, PlanLists* out);
+}  // namespace casim

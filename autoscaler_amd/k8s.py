@@ -182,6 +182,10 @@ class Node:
     unschedulable: bool = False
     annotations: dict = field(default_factory=dict)
     ready: bool = True                                 # NodeReady condition (kube_util.GetReadinessState)
+    capacity: Optional[dict] = None                    # Status.Capacity; None: equal to allocatable (BuildTestNode)
+
+    def get_capacity(self) -> dict:
+        return self.allocatable if self.capacity is None else self.capacity
 
 
 # ---------------------------------------------------------------------------

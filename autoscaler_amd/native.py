@@ -19,6 +19,12 @@ _LIB = None
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libcasim.so")
 
 
+# ca_estimate_plan_option_sums (csrc/expander.hip): list positions per block, and the most
+# score classes a block counts in LDS (above: a gather per id)
+OPTION_SUMS_TILE = 2048
+OPTION_SUMS_LDS_CLASSES = 2048
+
+
 class CasimError(RuntimeError):
     def __init__(self, status: int, what: str):
         self.status = status
@@ -87,6 +93,10 @@ def load() -> C.CDLL:
         "ca_estimate_plan_timings": ([vp, p(C.c_float), i32], C.c_int),
         "ca_estimate_plan_set_phase_timing": ([vp, i32], C.c_int),
         "ca_estimate_plan_group_ticks": ([vp, p(C.c_uint64), i32], C.c_int),
+        "ca_estimate_plan_option_sums": ([vp, vp, vp], C.c_int),
+        "ca_estimate_plan_option_sums_ms": ([vp, p(C.c_float)], C.c_int),
+        "ca_estimate_plan_fetch_group": ([vp, i32, vp, i32, p(i32)], C.c_int),
+        "ca_expander_best_options": ([i32, vp, vp, vp, vp, vp, vp, i32, vp, p(i32), vp], C.c_int),
         "ca_find_nodes_to_remove": ([vp, vp, i32, vp, vp, vp, vp, vp, p(i32), vp, vp], C.c_int),
         "ca_removal_stats": ([vp, p(i32), p(C.c_float), p(C.c_float)], C.c_int),
         "ca_removal_plan_create": ([vp, vp, i32, vp, vp, vp, vp, p(vp)], C.c_int),
@@ -186,6 +196,8 @@ def exported_symbols() -> list[str]:
         "ca_estimate_plan_timings",
         "ca_estimate_plan_set_phase_timing",
         "ca_estimate_plan_group_ticks", "ca_estimate_plan_fetch", "ca_estimate_plan_device_results",
+        "ca_estimate_plan_option_sums", "ca_estimate_plan_option_sums_ms", "ca_estimate_plan_fetch_group",
+        "ca_expander_best_options",
         "ca_go_sort_ranks",
         "ca_find_nodes_to_remove",
         "ca_removal_stats", "ca_removal_timings", "ca_removal_plan_create", "ca_removal_plan_run",
@@ -226,6 +238,23 @@ def sweep_compose(recs: np.ndarray, n_nodes: int, last_index: int) -> np.ndarray
     _check(load().ca_sweep_compose(r.ctypes.data, len(r), n_nodes, last_index, lin.ctypes.data, None),
            "ca_sweep_compose")
     return lin[: len(r)]
+
+
+def expander_best_options(filter_id: int, results: np.ndarray, req_milli_cpu, req_memory, cap_milli_cpu, cap_memory,
+                          options) -> tuple:
+    """ca_expander_best_options (host code, no device): Filter.BestOptions of least-waste /
+    most-pods over `options` (indices into the per-group arrays).  Returns (surviving
+    indices in input order, float64 score per input option)."""
+    res = np.ascontiguousarray(results, dtype=abi.ESTIMATE_RESULT_DTYPE)
+    opts = np.ascontiguousarray(options, dtype=np.int32)
+    i64 = [None if a is None else np.ascontiguousarray(a, dtype=np.int64)
+           for a in (req_milli_cpu, req_memory, cap_milli_cpu, cap_memory)]
+    best = np.zeros(max(len(opts), 1), np.int32)
+    scores = np.zeros(max(len(opts), 1), np.float64)
+    n = C.c_int32(0)
+    _check(load().ca_expander_best_options(filter_id, ptr(res), *[ptr(a) for a in i64], ptr(opts), len(opts),
+                                           ptr(best), C.byref(n), ptr(scores)), "ca_expander_best_options")
+    return best[: n.value], scores[: len(opts)]
 
 
 def device_count() -> int:
@@ -848,6 +877,31 @@ class EstimatePlan:
         out = np.full(max(self.total, 1), -1, np.int32)
         _check(self.lib.ca_estimate_plan_fetch(self.h, ptr(out)), "ca_estimate_plan_fetch")
         return out[: self.total]
+
+    def option_sums(self) -> tuple:
+        """resourcesForPods (waste.go:74-87) of every group of the last run, summed on the
+        device over the resident lists: (milli cpu [G], memory [G]) int64.  Raises CasimError
+        (CA_ESTATE) unless the last run left its final lists in device memory
+        (device_results=True always does)."""
+        cpu, mem = np.zeros(max(self.G, 1), np.int64), np.zeros(max(self.G, 1), np.int64)
+        _check(self.lib.ca_estimate_plan_option_sums(self.h, ptr(cpu), ptr(mem)), "ca_estimate_plan_option_sums")
+        return cpu[: self.G], mem[: self.G]
+
+    def option_sums_ms(self) -> float:
+        """Device time of the last option_sums kernel (ms)."""
+        ms = C.c_float(0)
+        _check(self.lib.ca_estimate_plan_option_sums_ms(self.h, C.byref(ms)), "ca_estimate_plan_option_sums_ms")
+        return ms.value
+
+    def fetch_group(self, g: int) -> np.ndarray:
+        """The scheduled pods of group `g` of the last run (n_scheduled ids), copied from
+        device memory; CA_ESTATE as option_sums."""
+        cap = int(self.group_off[g + 1] - self.group_off[g]) if 0 <= g < self.G else 0
+        out = np.full(max(cap, 1), -1, np.int32)
+        n = C.c_int32(0)
+        _check(self.lib.ca_estimate_plan_fetch_group(self.h, g, ptr(out), cap, C.byref(n)),
+               "ca_estimate_plan_fetch_group")
+        return out[: n.value]
 
     def stats(self) -> dict:
         r, a, b, c = C.c_int32(0), C.c_float(0), C.c_float(0), C.c_float(0)

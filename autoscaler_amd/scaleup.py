@@ -71,12 +71,10 @@ class ExpansionOption:
     pods: list
 
 
-def ComputeExpansionOptions(snapshot: ClusterSnapshot, checker: SchedulerBasedPredicateChecker,  # noqa: N802
-                            pod_groups: list, node_groups: list, limiter: ThresholdBasedEstimationLimiter):
-    """ComputeExpansionOption (orchestrator.go:443-491) for every (node group, template
-    NodeInfo) in ``node_groups``: pod groups' feasibility in one device call, then one
-    Estimate batch over the options that got pods.  Marks pod groups schedulable and
-    records their per-node-group predicate results, as the reference does."""
+def _feasible_pods(snapshot: ClusterSnapshot, pod_groups: list, node_groups: list):
+    """The feasibility matrix of ComputeExpansionOption (orchestrator.go:455-481) in one device
+    call; marks the pod groups.  Returns ([(pods, template NodeInfo)] of the node groups that
+    got pods, their indices in `node_groups`, the matrix)."""
     samples = [g.pods[0] for g in pod_groups]
     templates_api = [(t.node, list(t.pods)) for _, t in node_groups]
     snapshot.ensure(pods=[p for g in pod_groups for p in g.pods], templates=templates_api)
@@ -98,6 +96,16 @@ def ComputeExpansionOptions(snapshot: ClusterSnapshot, checker: SchedulerBasedPr
         if pods:
             est_groups.append((pods, info))
             est_index.append(k)
+    return est_groups, est_index, feas
+
+
+def ComputeExpansionOptions(snapshot: ClusterSnapshot, checker: SchedulerBasedPredicateChecker,  # noqa: N802
+                            pod_groups: list, node_groups: list, limiter: ThresholdBasedEstimationLimiter):
+    """ComputeExpansionOption (orchestrator.go:443-491) for every (node group, template
+    NodeInfo) in ``node_groups``: pod groups' feasibility in one device call, then one
+    Estimate batch over the options that got pods.  Marks pod groups schedulable and
+    records their per-node-group predicate results, as the reference does."""
+    est_groups, est_index, feas = _feasible_pods(snapshot, pod_groups, node_groups)
     options = [ExpansionOption(ng, 0, []) for ng, _ in node_groups]
     if est_groups:
         counts, scheduled = estimate_batch(checker, snapshot, est_groups, limiter)
@@ -107,4 +115,64 @@ def ComputeExpansionOptions(snapshot: ClusterSnapshot, checker: SchedulerBasedPr
     return options, feas
 
 
-__all__ = ["PodGroup", "BuildPodGroups", "ExpansionOption", "ComputeExpansionOptions", "NodeInfo", "Pod"]
+def ComputeBestExpansionOption(snapshot: ClusterSnapshot, checker: SchedulerBasedPredicateChecker,  # noqa: N802
+                               pod_groups: list, node_groups: list, limiter: ThresholdBasedEstimationLimiter,
+                               strategy):
+    """ComputeExpansionOptions followed by the orchestrator's option filter and
+    ExpanderStrategy.BestOption (orchestrator.go:139-195), with the options' pod lists left
+    in device memory: one Estimate plan run with device results, the `len(Pods) > 0 &&
+    NodeCount > 0` filter (:174) on its counts, `strategy` (an expander.ChainStrategy) on
+    the device form of its filters, and one copy of the pod list of each option that is left
+    (one option unless the chain fell through to the fallback).  Returns (the best
+    ExpansionOption or None, the feasibility matrix); the snapshot's backend must be the
+    device mirror."""
+    from . import native
+    from .expander import DeviceOptions, resources_for_node
+    from .predicatechecker import unsupported
+    from .scope import UnsupportedByKernels, out_of_scope_reason
+
+    if not isinstance(snapshot.backend, native.Mirror):
+        raise TypeError("ComputeBestExpansionOption reads the Estimate plan's device-resident lists: "
+                        "the snapshot's backend must be native.Mirror")
+    est_groups, est_index, feas = _feasible_pods(snapshot, pod_groups, node_groups)
+    if not est_groups:
+        return None, feas
+    all_pods, offs = [], [0]
+    for pods, _ in est_groups:
+        all_pods.extend(pods)
+        offs.append(len(all_pods))
+    table = snapshot.interner.encode_pods(all_pods)
+    templates = np.zeros(len(est_groups), abi.TEMPLATE_DTYPE)
+    for g, (_, info) in enumerate(est_groups):
+        templates[g] = snapshot.interner.encode_template(info.node, list(info.pods))
+    caps = [resources_for_node(info.node) for _, info in est_groups]
+    with unsupported("Estimate: the snapshot holds a pod with required anti-affinity"):
+        plan = native.EstimatePlan(snapshot.backend, table, np.array(offs, np.int32),
+                                   np.arange(len(all_pods), dtype=np.int32), templates)
+    with plan:
+        with unsupported("Estimate: the snapshot holds a pod with required anti-affinity"):
+            out = plan.run(limiter.max_nodes, checker.last_index, device_results=True)
+        for g, r in enumerate(out.results):
+            if int(r["status"]) == abi.CA_EUNSUPPORTED:
+                why = next((out_of_scope_reason(p) for p in est_groups[g][0] if out_of_scope_reason(p)), None)
+                raise UnsupportedByKernels(f"node group {g}: " + (why or "pods depend on node identity (hostname / "
+                                                                          "nodeName) or template pods need InterPodAffinity"))
+            checker.evals += int(r["evals"])
+        checker.last_index = out.last_index
+        valid = [g for g, r in enumerate(out.results) if int(r["n_scheduled"]) > 0 and int(r["node_count"]) > 0]
+        dev = DeviceOptions(plan, out.results, [c for c, _ in caps], [m for _, m in caps])
+        if not valid:                      # "No expansion options" (orchestrator.go:181-188)
+            return None, feas
+        options = []
+        for g in strategy.best_indices(dev, valid):
+            ng = node_groups[est_index[g]][0]
+            pods = [all_pods[i] for i in plan.fetch_group(int(g))]
+            options.append(ExpansionOption(ng, int(out.results[g]["node_count"]), pods))
+    if len(options) == 1:
+        return options[0], feas
+    node_infos = {(ng.Id() if hasattr(ng, "Id") else ng): info for ng, info in node_groups}
+    return strategy.fallback.BestOption(options, node_infos), feas
+
+
+__all__ = ["PodGroup", "BuildPodGroups", "ExpansionOption", "ComputeExpansionOptions", "ComputeBestExpansionOption",
+           "NodeInfo", "Pod"]

@@ -464,6 +464,42 @@ int ca_estimate_plan_rebase(const ca_estimate_plan* p, ca_estimate_result* resul
  * not placed by the closed-form run path) in bits 32-63.  Returns the group count. */
 int ca_estimate_plan_group_ticks(const ca_estimate_plan* p, uint64_t* out, int32_t cap);
 
+/* ---- expander: least-waste and most-pods over the resident Estimate results ----
+ * ExpanderStrategy.BestOption (CA/core/scaleup/orchestrator/orchestrator.go:195) follows
+ * Estimate.  most-pods needs n_scheduled only; least-waste sums the container requests of
+ * every scheduled pod of every option — on the device, so a caller that keeps the lists in
+ * HBM (ca_estimate_plan_run with sched_pod == NULL) picks first and copies one list after. */
+/* resourcesForPods (expander/waste/waste.go:74-87) for every option of the last run, from
+ * the plan's device-resident lists: G values each.  CA_ESTATE when the last run did not
+ * leave its final lists in device memory (run with sched_pod == NULL).  The sums are
+ * per-pod MilliValue / Value int64s (ca_pod_spec.score_milli_cpu / score_memory) added as
+ * wrapping int64: the reference's Quantity sums when every request is a whole milli-unit
+ * and the sums stay below 2^63.  A group whose status is not CA_OK sums to 0. */
+int ca_estimate_plan_option_sums(ca_estimate_plan* p, int64_t* req_milli_cpu, int64_t* req_memory);
+/* device time (HIP events) of the last ca_estimate_plan_option_sums kernel, ms; 0 when that
+ * call launched none */
+int ca_estimate_plan_option_sums_ms(const ca_estimate_plan* p, float* kernel_ms);
+/* the scheduled pods of one group of the last run (one D2H of n_scheduled ids).  *n =
+ * n_scheduled; CA_ECAPACITY when cap is short (nothing copied), CA_ESTATE as above. */
+int ca_estimate_plan_fetch_group(const ca_estimate_plan* p, int32_t group, int32_t* sched_pod,
+                                 int32_t cap, int32_t* n);
+#define CA_EXPANDER_MOST_PODS   1   /* expander/mostpods/mostpods.go:33-53 */
+#define CA_EXPANDER_LEAST_WASTE 2   /* expander/waste/waste.go:36-72       */
+/* Filter.BestOptions over options[0..n_options) (indices into the per-group arrays, in the
+ * caller's option order).  best[] (n_options slots) receives the surviving indices in input
+ * order, *n_best their number.  scores (may be NULL): wastedScore per input option (most-pods:
+ * its pod count).  Host code, no device needed.  least-waste, per option o: avail = cap[o] x
+ * results[o].node_count in int64, wasted = float64(avail - req[o]) / float64(avail) per
+ * resource, score = wastedCPU + wastedMemory; `==` against the running least score (from 0)
+ * is tested before `nil || <`, so a NaN score (0 / 0 at node_count 0) survives only as the
+ * first option.  cap_* is the node's Capacity (resourcesForNode, waste.go:89-94), not the
+ * Allocatable of ca_template.  most-pods ignores req_* / cap_* (may be NULL). */
+int ca_expander_best_options(int32_t filter, const ca_estimate_result* results,
+                             const int64_t* req_milli_cpu, const int64_t* req_memory,
+                             const int64_t* cap_milli_cpu, const int64_t* cap_memory,
+                             const int32_t* options, int32_t n_options,
+                             int32_t* best, int32_t* n_best, double* scores);
+
 /* ---- removal simulator ------------------------------------------------------- */
 /* FindNodesToRemove(candidates, destinations) with legacy semantics (canPersist=false).
  * cand_status[c] != 0 carries the host-side GetPodsToMove verdict (drain.go:50-90):
