@@ -2608,6 +2608,7 @@ struct ca_estimate_plan {
     bool lists_final = false;
     std::vector<int32_t> last_nsched;
     mutable OptionSumsScratch opt_scratch;
+    mutable MissingPodsScratch missing_scratch;      // nodegroupset.hip
     ~ca_estimate_plan();
 };
 
@@ -3906,6 +3907,7 @@ void estimate_plan_lists(const ca_estimate_plan* p, PlanLists* out) {
     out->d_sched_pod = p->d_sched_pod.as<int32_t>();
     out->final_lists = p->lists_final && (int32_t)p->last_nsched.size() == p->G;
     out->scratch = &p->opt_scratch;
+    out->missing = &p->missing_scratch;
 }
 }  // namespace casim
 

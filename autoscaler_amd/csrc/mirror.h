@@ -352,7 +352,23 @@ struct OptionSumsScratch {
     }
 };
 
-// What expander.hip reads of an Estimate plan (the struct itself is private to estimate.hip).
+// Buffers and events of ca_estimate_plan_groups_missing_pods (nodegroupset.hip), kept in the
+// plan like OptionSumsScratch.
+struct MissingPodsScratch {
+    DevBuf d_in, d_out;             // [off | n_scheduled | tile prefix] of the rows; [n_missing | bad ids | first]
+    DevBuf d_rows;                  // one batch of bitmap rows over the pod set
+    HostBuf h;                      // page-locked staging of d_in and d_out
+    std::vector<int32_t> row_of, row_group;   // group -> row or -1; row -> group
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    bool timed = false;             // ev0 / ev1 bracket the kernels of the last call
+    ~MissingPodsScratch() {
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+    }
+};
+
+// What expander.hip and nodegroupset.hip read of an Estimate plan (the struct itself is private
+// to estimate.hip).
 struct PlanLists {
     ca_mirror* m = nullptr;
     const ca_podset* s = nullptr;
@@ -362,6 +378,7 @@ struct PlanLists {
     const int32_t* d_sched_pod = nullptr;  // the device lists, sched_pod layout
     bool final_lists = false;              // the last run left its final ids in d_sched_pod
     OptionSumsScratch* scratch = nullptr;
+    MissingPodsScratch* missing = nullptr;
 };
 void estimate_plan_lists(const ca_estimate_plan* p, PlanLists* out);
 }  // namespace casim

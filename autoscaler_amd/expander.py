@@ -13,7 +13,10 @@ Two forms of each filter:
 
 ``ChainStrategy`` is expander/factory/chain.go:37-46: filters in order, the first that leaves
 one option decides, otherwise the caller's fallback strategy (the reference's is random)
-picks among the rest.  The price, priority and gRPC expanders stay with the caller.
+picks among the rest.  The price, priority and gRPC expanders stay with the caller.  What
+follows BestOption when similar node groups are balanced (FindSimilarNodeGroups,
+filterNodeGroupsByPods on the same resident lists, BalanceScaleUpBetweenGroups) is
+``nodegroupset.py`` and ``scaleup.ComputeBalancedScaleUp``.
 
 Requests are summed on the device as per-pod MilliValue / Value int64s (the podset's
 containers-only score fields): equal to the reference's Quantity sums when every request is

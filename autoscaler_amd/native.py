@@ -23,6 +23,12 @@ LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libc
 # score classes a block counts in LDS (above: a gather per id)
 OPTION_SUMS_TILE = 2048
 OPTION_SUMS_LDS_CLASSES = 2048
+# ca_estimate_plan_groups_missing_pods (csrc/nodegroupset.hip): list positions per block, the
+# most candidate rows one block of the test kernel walks, and the default bound on the bitmap
+# rows resident at once (bytes; CASIM_MISSING_SCRATCH under CASIM_KNOBS overrides it per call)
+MISSING_PODS_TILE = 2048
+MISSING_PODS_ROWS = 64
+MISSING_PODS_SCRATCH = 64 << 20
 
 
 class CasimError(RuntimeError):
@@ -97,6 +103,8 @@ def load() -> C.CDLL:
         "ca_estimate_plan_option_sums_ms": ([vp, p(C.c_float)], C.c_int),
         "ca_estimate_plan_fetch_group": ([vp, i32, vp, i32, p(i32)], C.c_int),
         "ca_expander_best_options": ([i32, vp, vp, vp, vp, vp, vp, i32, vp, p(i32), vp], C.c_int),
+        "ca_estimate_plan_groups_missing_pods": ([vp, i32, vp, i32, vp, vp], C.c_int),
+        "ca_estimate_plan_groups_missing_pods_ms": ([vp, p(C.c_float)], C.c_int),
         "ca_find_nodes_to_remove": ([vp, vp, i32, vp, vp, vp, vp, vp, p(i32), vp, vp], C.c_int),
         "ca_removal_stats": ([vp, p(i32), p(C.c_float), p(C.c_float)], C.c_int),
         "ca_removal_plan_create": ([vp, vp, i32, vp, vp, vp, vp, p(vp)], C.c_int),
@@ -198,6 +206,7 @@ def exported_symbols() -> list[str]:
         "ca_estimate_plan_group_ticks", "ca_estimate_plan_fetch", "ca_estimate_plan_device_results",
         "ca_estimate_plan_option_sums", "ca_estimate_plan_option_sums_ms", "ca_estimate_plan_fetch_group",
         "ca_expander_best_options",
+        "ca_estimate_plan_groups_missing_pods", "ca_estimate_plan_groups_missing_pods_ms",
         "ca_go_sort_ranks",
         "ca_find_nodes_to_remove",
         "ca_removal_stats", "ca_removal_timings", "ca_removal_plan_create", "ca_removal_plan_run",
@@ -902,6 +911,25 @@ class EstimatePlan:
         _check(self.lib.ca_estimate_plan_fetch_group(self.h, g, ptr(out), cap, C.byref(n)),
                "ca_estimate_plan_fetch_group")
         return out[: n.value]
+
+    def groups_missing_pods(self, required: int, groups) -> tuple:
+        """filterNodeGroupsByPods (orchestrator.go:596-628) on the last run's resident lists:
+        per entry of `groups`, (how many positions of group `required`'s list name a pod that
+        the entry's list lacks, the first such position or -1) as int32 arrays.  A group is kept
+        by the reference iff its count is 0.  Pods are compared by pod-set index, so the groups'
+        pod_idx slices must index one shared pod table.  CA_ESTATE as option_sums."""
+        gs = np.ascontiguousarray(groups, dtype=np.int32)
+        n_missing, first = np.zeros(max(len(gs), 1), np.int32), np.full(max(len(gs), 1), -1, np.int32)
+        _check(self.lib.ca_estimate_plan_groups_missing_pods(self.h, int(required), ptr(gs), len(gs), ptr(n_missing),
+                                                             ptr(first)), "ca_estimate_plan_groups_missing_pods")
+        return n_missing[: len(gs)], first[: len(gs)]
+
+    def groups_missing_pods_ms(self) -> float:
+        """Device time of the last groups_missing_pods call's kernels (ms); 0 if it launched none."""
+        ms = C.c_float(0)
+        _check(self.lib.ca_estimate_plan_groups_missing_pods_ms(self.h, C.byref(ms)),
+               "ca_estimate_plan_groups_missing_pods_ms")
+        return ms.value
 
     def stats(self) -> dict:
         r, a, b, c = C.c_int32(0), C.c_float(0), C.c_float(0), C.c_float(0)

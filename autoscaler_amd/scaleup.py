@@ -174,5 +174,84 @@ def ComputeBestExpansionOption(snapshot: ClusterSnapshot, checker: SchedulerBase
     return strategy.fallback.BestOption(options, node_infos), feas
 
 
+def ComputeBalancedScaleUp(snapshot: ClusterSnapshot, checker: SchedulerBasedPredicateChecker,  # noqa: N802
+                           pod_groups: list, node_groups: list, limiter: ThresholdBasedEstimationLimiter,
+                           strategy, processor, cap_new_nodes=None):
+    """ScaleUp from the options to the final scale-up plan (orchestrator.go:139-313) with
+    --balance-similar-node-groups, the options' pod lists left in device memory: the
+    feasibility matrix; ONE Estimate plan over a shared pod table (every pending pod encoded
+    once, each group's pod_idx slice naming its feasible pods in that table, so a pod has one
+    id in every group); a run with device results; the :174 filter; `strategy` on the device
+    form of its filters (its fallback gets the fetched survivors); `cap_new_nodes(node_count)`
+    if given (the caller's GetCappedNewNodeCount / ApplyLimits; IsNodeGroupSafeToScaleUp stays
+    with the caller too); `processor.FindSimilarNodeGroups`; the similar groups that have an
+    option and whose option holds every pod of the winner's (filterNodeGroupsByPods :596-628,
+    on the device: nodegroupset.filter_plan_groups_by_pods);
+    `processor.BalanceScaleUpBetweenGroups([best] + kept, new_nodes)`; one copy of the winner's
+    list.  The node groups are objects with Id() / TargetSize() / MaxSize().  Returns (the best
+    ExpansionOption or None, [ScaleUpInfo], the feasibility matrix)."""
+    from . import native
+    from .expander import DeviceOptions, resources_for_node
+    from .nodegroupset import filter_plan_groups_by_pods
+    from .predicatechecker import unsupported
+    from .scope import UnsupportedByKernels, out_of_scope_reason
+
+    if not isinstance(snapshot.backend, native.Mirror):
+        raise TypeError("ComputeBalancedScaleUp reads the Estimate plan's device-resident lists: "
+                        "the snapshot's backend must be native.Mirror")
+    est_groups, est_index, feas = _feasible_pods(snapshot, pod_groups, node_groups)
+    if not est_groups:
+        return None, [], feas
+    all_pods, row = [], {}
+    pod_idx, offs = [], [0]
+    for pods, _ in est_groups:                  # the shared table: every feasible pod once
+        for p in pods:
+            if id(p) not in row:
+                row[id(p)] = len(all_pods)
+                all_pods.append(p)
+            pod_idx.append(row[id(p)])
+        offs.append(len(pod_idx))
+    table = snapshot.interner.encode_pods(all_pods)
+    templates = np.zeros(len(est_groups), abi.TEMPLATE_DTYPE)
+    for g, (_, info) in enumerate(est_groups):
+        templates[g] = snapshot.interner.encode_template(info.node, list(info.pods))
+    caps = [resources_for_node(info.node) for _, info in est_groups]
+    with unsupported("Estimate: the snapshot holds a pod with required anti-affinity"):
+        plan = native.EstimatePlan(snapshot.backend, table, np.array(offs, np.int32), np.array(pod_idx, np.int32),
+                                   templates)
+    node_infos = {ng.Id(): info for ng, info in node_groups}
+    with plan:
+        with unsupported("Estimate: the snapshot holds a pod with required anti-affinity"):
+            out = plan.run(limiter.max_nodes, checker.last_index, device_results=True)
+        for g, r in enumerate(out.results):
+            if int(r["status"]) == abi.CA_EUNSUPPORTED:
+                why = next((out_of_scope_reason(p) for p in est_groups[g][0] if out_of_scope_reason(p)), None)
+                raise UnsupportedByKernels(f"node group {g}: " + (why or "pods depend on node identity (hostname / "
+                                                                          "nodeName) or template pods need InterPodAffinity"))
+            checker.evals += int(r["evals"])
+        checker.last_index = out.last_index
+        valid = [g for g, r in enumerate(out.results) if int(r["n_scheduled"]) > 0 and int(r["node_count"]) > 0]
+        if not valid:                      # "No expansion options" (orchestrator.go:181-188)
+            return None, [], feas
+        dev = DeviceOptions(plan, out.results, [c for c, _ in caps], [m for _, m in caps])
+        group_of = {node_groups[est_index[g]][0].Id(): g for g in valid}      # expansionOptions' keys
+
+        def option(g):
+            return ExpansionOption(node_groups[est_index[g]][0], int(out.results[g]["node_count"]),
+                                   [all_pods[i] for i in plan.fetch_group(int(g))])
+
+        left = [int(g) for g in strategy.best_indices(dev, valid)]
+        best = option(left[0]) if len(left) == 1 else strategy.fallback.BestOption([option(g) for g in left], node_infos)
+        if best is None or best.node_count <= 0:          # :196-202
+            return None, [], feas
+        best_g = group_of[best.node_group.Id()]
+        new_nodes = best.node_count if cap_new_nodes is None else cap_new_nodes(best.node_count)
+        similar = processor.FindSimilarNodeGroups([ng for ng, _ in node_groups], best.node_group, node_infos)
+        with_option = [ng for ng in similar if ng.Id() in group_of]
+        fit = set(filter_plan_groups_by_pods(plan, best_g, [group_of[ng.Id()] for ng in with_option]))
+        kept = [ng for ng in with_option if group_of[ng.Id()] in fit]
+    return best, processor.BalanceScaleUpBetweenGroups([best.node_group] + kept, new_nodes), feas
+
+
 __all__ = ["PodGroup", "BuildPodGroups", "ExpansionOption", "ComputeExpansionOptions", "ComputeBestExpansionOption",
-           "NodeInfo", "Pod"]
+           "ComputeBalancedScaleUp", "NodeInfo", "Pod"]

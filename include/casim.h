@@ -499,6 +499,31 @@ int ca_expander_best_options(int32_t filter, const ca_estimate_result* results,
                              const int64_t* cap_milli_cpu, const int64_t* cap_memory,
                              const int32_t* options, int32_t n_options,
                              int32_t* best, int32_t* n_best, double* scores);
+/* filterNodeGroupsByPods (orchestrator.go:596-628) on the last run's device-resident lists.
+ * For every k < n_groups:
+ *   n_missing[k]     = number of positions i < n_scheduled[required_group] whose pod id does
+ *                      not occur in the first n_scheduled[groups[k]] ids of group groups[k]
+ *   first_missing[k] = the smallest such position, -1 when there is none
+ * The reference's loop breaks at the first such position and names that pod in its log line
+ * (:615-620).
+ * A group is kept by the reference iff n_missing == 0.  first_missing may be NULL.
+ * Pods are compared by pod-set index where Go compares *apiv1.Pod pointers: the call means
+ * what the reference means only when the groups' pod_idx slices index one shared pod set, so
+ * that one pod has one id in every group.  Membership is a set test: either list may repeat an
+ * id, and every position of the required list is answered on its own.  groups[] may contain
+ * required_group (0 / -1) and may repeat a group; each slot is answered independently.  A group
+ * whose status is not CA_OK has n_scheduled 0: as a candidate it misses every position
+ * (n_missing = n_scheduled[required_group], first_missing 0 when that is > 0), as the required
+ * group it makes every candidate fit.  CA_ESTATE as ca_estimate_plan_option_sums; CA_EINVAL for
+ * a group index outside [0, G) or a NULL output with n_groups > 0; CA_EDEVICE when a counted
+ * position of either list holds an id outside the pod set (such ids are skipped and counted);
+ * CA_ECAPACITY when one bitmap row over the pod set (4 bytes per 32 pods) exceeds the scratch
+ * bound (64 MiB).  n_groups == 0 or an empty required list: CA_OK without a launch. */
+int ca_estimate_plan_groups_missing_pods(ca_estimate_plan* p, int32_t required_group,
+                                         const int32_t* groups, int32_t n_groups,
+                                         int32_t* n_missing, int32_t* first_missing);
+/* device time (HIP events) of the last call's kernels, ms; 0 when it launched none */
+int ca_estimate_plan_groups_missing_pods_ms(const ca_estimate_plan* p, float* kernel_ms);
 
 /* ---- removal simulator ------------------------------------------------------- */
 /* FindNodesToRemove(candidates, destinations) with legacy semantics (canPersist=false).
