@@ -2609,6 +2609,7 @@ struct ca_estimate_plan {
     std::vector<int32_t> last_nsched;
     mutable OptionSumsScratch opt_scratch;
     mutable MissingPodsScratch missing_scratch;      // nodegroupset.hip
+    mutable PriceSumsScratch price_scratch;          // expander.hip
     ~ca_estimate_plan();
 };
 
@@ -3908,6 +3909,7 @@ void estimate_plan_lists(const ca_estimate_plan* p, PlanLists* out) {
     out->final_lists = p->lists_final && (int32_t)p->last_nsched.size() == p->G;
     out->scratch = &p->opt_scratch;
     out->missing = &p->missing_scratch;
+    out->price = &p->price_scratch;
 }
 }  // namespace casim
 

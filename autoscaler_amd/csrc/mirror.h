@@ -367,6 +367,19 @@ struct MissingPodsScratch {
     }
 };
 
+// Buffers and events of ca_estimate_plan_option_price_sums (expander.hip), kept in the plan
+// like OptionSumsScratch.
+struct PriceSumsScratch {
+    DevBuf d_in, d_price, d_out;    // [off | n_scheduled | launch order] of the groups; the pod prices; G totals + bad ids
+    HostBuf h;                      // page-locked staging of all three
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    bool timed = false;             // ev0 / ev1 bracket the kernel of the last call
+    ~PriceSumsScratch() {
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+    }
+};
+
 // What expander.hip and nodegroupset.hip read of an Estimate plan (the struct itself is private
 // to estimate.hip).
 struct PlanLists {
@@ -379,6 +392,7 @@ struct PlanLists {
     bool final_lists = false;              // the last run left its final ids in d_sched_pod
     OptionSumsScratch* scratch = nullptr;
     MissingPodsScratch* missing = nullptr;
+    PriceSumsScratch* price = nullptr;
 };
 void estimate_plan_lists(const ca_estimate_plan* p, PlanLists* out);
 }  // namespace casim

@@ -23,6 +23,10 @@ LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libc
 # score classes a block counts in LDS (above: a gather per id)
 OPTION_SUMS_TILE = 2048
 OPTION_SUMS_LDS_CLASSES = 2048
+# ca_estimate_plan_option_price_sums (csrc/expander.hip): list positions a wave hands to its add
+# chain per step, and options (waves) per block
+PRICE_SUMS_CHUNK = 256
+PRICE_SUMS_WAVES = 4
 # ca_estimate_plan_groups_missing_pods (csrc/nodegroupset.hip): list positions per block, the
 # most candidate rows one block of the test kernel walks, and the default bound on the bitmap
 # rows resident at once (bytes; CASIM_MISSING_SCRATCH under CASIM_KNOBS overrides it per call)
@@ -101,6 +105,8 @@ def load() -> C.CDLL:
         "ca_estimate_plan_group_ticks": ([vp, p(C.c_uint64), i32], C.c_int),
         "ca_estimate_plan_option_sums": ([vp, vp, vp], C.c_int),
         "ca_estimate_plan_option_sums_ms": ([vp, p(C.c_float)], C.c_int),
+        "ca_estimate_plan_option_price_sums": ([vp, vp, i32, vp], C.c_int),
+        "ca_estimate_plan_option_price_sums_ms": ([vp, p(C.c_float)], C.c_int),
         "ca_estimate_plan_fetch_group": ([vp, i32, vp, i32, p(i32)], C.c_int),
         "ca_expander_best_options": ([i32, vp, vp, vp, vp, vp, vp, i32, vp, p(i32), vp], C.c_int),
         "ca_estimate_plan_groups_missing_pods": ([vp, i32, vp, i32, vp, vp], C.c_int),
@@ -205,7 +211,7 @@ def exported_symbols() -> list[str]:
         "ca_estimate_plan_set_phase_timing",
         "ca_estimate_plan_group_ticks", "ca_estimate_plan_fetch", "ca_estimate_plan_device_results",
         "ca_estimate_plan_option_sums", "ca_estimate_plan_option_sums_ms", "ca_estimate_plan_fetch_group",
-        "ca_expander_best_options",
+        "ca_expander_best_options", "ca_estimate_plan_option_price_sums", "ca_estimate_plan_option_price_sums_ms",
         "ca_estimate_plan_groups_missing_pods", "ca_estimate_plan_groups_missing_pods_ms",
         "ca_go_sort_ranks",
         "ca_find_nodes_to_remove",
@@ -900,6 +906,27 @@ class EstimatePlan:
         """Device time of the last option_sums kernel (ms)."""
         ms = C.c_float(0)
         _check(self.lib.ca_estimate_plan_option_sums_ms(self.h, C.byref(ms)), "ca_estimate_plan_option_sums_ms")
+        return ms.value
+
+    def option_price_sums(self, pod_price) -> np.ndarray:
+        """totalPodPrice of the price expander (price.go:126-134) of every group of the last run:
+        the left-to-right float64 sum of `pod_price` (one value per pod of the plan's pod set, in
+        pod-set index order; NaN for a pod whose PodPrice failed) over each resident list, [G]
+        float64, bit for bit the reference's loop.  CA_ESTATE as option_sums; CA_EINVAL unless
+        len(pod_price) is the pod set's size."""
+        price = np.ascontiguousarray(pod_price, dtype=np.float64)
+        if price.ndim != 1:
+            raise ValueError("pod_price: one value per pod of the pod set")
+        out = np.zeros(max(self.G, 1), np.float64)
+        _check(self.lib.ca_estimate_plan_option_price_sums(self.h, ptr(price), len(price), ptr(out)),
+               "ca_estimate_plan_option_price_sums")
+        return out[: self.G]
+
+    def option_price_sums_ms(self) -> float:
+        """Device time of the last option_price_sums kernel (ms)."""
+        ms = C.c_float(0)
+        _check(self.lib.ca_estimate_plan_option_price_sums_ms(self.h, C.byref(ms)),
+               "ca_estimate_plan_option_price_sums_ms")
         return ms.value
 
     def fetch_group(self, g: int) -> np.ndarray:

@@ -160,7 +160,9 @@ def ComputeBestExpansionOption(snapshot: ClusterSnapshot, checker: SchedulerBase
             checker.evals += int(r["evals"])
         checker.last_index = out.last_index
         valid = [g for g, r in enumerate(out.results) if int(r["n_scheduled"]) > 0 and int(r["node_count"]) > 0]
-        dev = DeviceOptions(plan, out.results, [c for c, _ in caps], [m for _, m in caps])
+        dev = DeviceOptions(plan, out.results, [c for c, _ in caps], [m for _, m in caps], pods=all_pods,
+                            node_groups=[node_groups[k][0] for k in est_index],
+                            node_infos={(ng.Id() if hasattr(ng, "Id") else ng): info for ng, info in node_groups})
         if not valid:                      # "No expansion options" (orchestrator.go:181-188)
             return None, feas
         options = []
@@ -233,7 +235,8 @@ def ComputeBalancedScaleUp(snapshot: ClusterSnapshot, checker: SchedulerBasedPre
         valid = [g for g, r in enumerate(out.results) if int(r["n_scheduled"]) > 0 and int(r["node_count"]) > 0]
         if not valid:                      # "No expansion options" (orchestrator.go:181-188)
             return None, [], feas
-        dev = DeviceOptions(plan, out.results, [c for c, _ in caps], [m for _, m in caps])
+        dev = DeviceOptions(plan, out.results, [c for c, _ in caps], [m for _, m in caps], pods=all_pods,
+                            node_groups=[node_groups[k][0] for k in est_index], node_infos=node_infos)
         group_of = {node_groups[est_index[g]][0].Id(): g for g in valid}      # expansionOptions' keys
 
         def option(g):

@@ -479,6 +479,30 @@ int ca_estimate_plan_option_sums(ca_estimate_plan* p, int64_t* req_milli_cpu, in
 /* device time (HIP events) of the last ca_estimate_plan_option_sums kernel, ms; 0 when that
  * call launched none */
 int ca_estimate_plan_option_sums_ms(const ca_estimate_plan* p, float* kernel_ms);
+/* totalPodPrice of the price expander (expander/price/price.go:126-134) for every option of the
+ * last run, from the plan's device-resident lists.  pod_price[i] is PricingModel.PodPrice of
+ * pod i of the plan's pod set, one value per pod in pod-set index order; n_prices must equal
+ * the pod set's size.  The prices are uploaded on each call.  For every group g, with n =
+ * n_scheduled[g] and id_k the k-th id of g's list in list order,
+ *   total_pod_price[g] = ((...((+0.0 + price[id_0]) + price[id_1]) ...) + price[id_{n-1}])
+ * where each + is one IEEE-754 binary64 add, round to nearest even, subnormals kept: the
+ * reference's left-to-right float64 sum bit for bit.  A group whose status is not CA_OK, or with
+ * n == 0, sums to +0.0.  Only the n counted positions enter the chain.
+ * A pod whose PodPrice failed: pass NaN for it.  NaN propagates, so the total of every option
+ * that holds the pod is NaN and the caller skips that option — the reference's `continue
+ * nextoption`.  NaN is therefore reserved: a pricing model must not return it as a price, and
+ * +inf and -inf in one list (NaN as well) also read as "skip".
+ * The scoring that follows (priceSubScore, the math.Tanh suppression, the comparisons of
+ * price.go:141-185) is a few operations per option and stays with the caller, in the caller's
+ * own math library.
+ * CA_ESTATE as ca_estimate_plan_option_sums; CA_EINVAL for NULL arguments or a wrong n_prices;
+ * CA_EDEVICE when a counted position holds an id outside the pod set (such ids are skipped and
+ * counted); G == 0: CA_OK without a launch. */
+int ca_estimate_plan_option_price_sums(ca_estimate_plan* p, const double* pod_price,
+                                       int32_t n_prices, double* total_pod_price);
+/* device time (HIP events) of the last ca_estimate_plan_option_price_sums kernel, ms; 0 when
+ * that call launched none */
+int ca_estimate_plan_option_price_sums_ms(const ca_estimate_plan* p, float* kernel_ms);
 /* the scheduled pods of one group of the last run (one D2H of n_scheduled ids).  *n =
  * n_scheduled; CA_ECAPACITY when cap is short (nothing copied), CA_ESTATE as above. */
 int ca_estimate_plan_fetch_group(const ca_estimate_plan* p, int32_t group, int32_t* sched_pod,
