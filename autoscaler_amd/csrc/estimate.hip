@@ -771,6 +771,23 @@ __host__ __device__ inline size_t pdq_lds_bytes(int32_t lds_n) {
     return (3 * np + np / 8 + 2 * (np / 64 + 1) + 15) & ~(size_t)15;
 }
 
+// Two-launch sort of the decoupled path: lists longer than FAN_MIN positions stop after the
+// workgroup step that leaves FAN_PARTS long frames pending (FAN_TOP_STEPS steps at most)
+// and finish in up to FAN_PARTS part workgroups.  Knobs (diagnostics): CASIM_SORT_FAN=0
+// turns it off, CASIM_SORT_FAN_MIN / _PARTS / _STEPS replace the defaults.
+constexpr int32_t FAN_MIN = 8192, FAN_PARTS = 8, FAN_TOP_STEPS = 4;
+inline void fan_knobs(int32_t* parts, int32_t* fmin, int32_t* steps) {
+    *parts = FAN_PARTS;
+    *fmin = FAN_MIN;
+    *steps = FAN_TOP_STEPS;
+    if (const char* e = knob_env("CASIM_SORT_FAN_PARTS")) *parts = atoi(e);
+    if (const char* e = knob_env("CASIM_SORT_FAN_MIN")) *fmin = std::max(0, atoi(e));
+    if (const char* e = knob_env("CASIM_SORT_FAN_STEPS")) *steps = atoi(e);
+    *parts = std::min(std::max(*parts, 1), (int32_t)pdq::FAN_PARTS_MAX);
+    *steps = std::min(std::max(*steps, 1), (int32_t)pdq::FAN_STEPS_MAX);
+    if (const char* e = knob_env("CASIM_SORT_FAN")) if (atoi(e) == 0) *parts = 0;
+}
+
 #ifndef CASIM_PDQ_UB
 #define CASIM_PDQ_UB 8
 #endif
@@ -783,10 +800,15 @@ __global__ void __launch_bounds__(pdq::NT) k_pdq_sort(const GroupMeta* __restric
                                                      uint32_t* __restrict__ sorted, uint64_t* __restrict__ gE,
                                                      uint64_t* __restrict__ xs_all, pdq::Frame* __restrict__ stack_all,
                                                      int32_t lds_n, int32_t force, int32_t limit0, const int32_t* __restrict__ gmap,
-                                                     int32_t* __restrict__ ids_out, int32_t* __restrict__ ids_ready,
+                                                     int32_t* __restrict__ ids_out, int32_t* __restrict__ fan,
                                                      int32_t ids_epoch, const int32_t* __restrict__ item_cls,
                                                      const ca_template* __restrict__ tmpls,
-                                                     const int64_t* __restrict__ cls_sc, int32_t NP) {
+                                                     const int64_t* __restrict__ cls_sc, int32_t NP,
+                                                     int32_t fan_parts, int32_t fan_min, int32_t fan_steps) {
+    // fan != null: the group's record of the fan table (pdqsort.h FAN_*) is written — the
+    // part bounds and ready flags the publisher waits on.  fan_parts > 0: an LDS-store sort
+    // of more than fan_min positions runs only its top phase here and hands its pending
+    // frames to k_pdq_sort_parts (below); every other sort ends here as one part.
     extern __shared__ __align__(16) unsigned char pdq_dyn[];
     __shared__ pdq::Ctl ctl;
 #ifdef CASIM_PROF
@@ -893,7 +915,41 @@ __global__ void __launch_bounds__(pdq::NT) k_pdq_sort(const GroupMeta* __restric
 #ifdef CASIM_PROF
         const uint64_t t_k1 = clock64();
 #endif
-        pdq::wg_sort(st, n, stack, n / 2 + 2, scr, ctl, limit0);
+        // (one call of the step loop for both forms: its code is the kernel's largest part)
+        const bool fanned = fan && fan_parts > 0 && n > fan_min;
+        const int cap = n / 2 + 2;
+        pdq::wg_sort_root<pdq::LdsStore>(n, stack, cap, ctl, limit0);
+        pdq::wg_steps(st, n, stack, cap, scr, ctl, fanned ? fan_parts : 0, fan_steps);
+#ifdef CASIM_PROF
+        const uint64_t t_k2f = clock64();
+#endif
+        if (fanned) {
+            // top phase: the steps stopped with enough long frames pending; the store (position
+            // and rank per element; gE is otherwise unused by this store), the frame counts
+            // and the split go to global memory.  The frames are in `stack` already.
+            uint32_t* spill = reinterpret_cast<uint32_t*>(gE + off);
+            for (int32_t i = tid; i < n; i += pdq::NT) spill[i] = st.ld(i);
+            int32_t* fr = fan + (size_t)gi * pdq::FAN_STRIDE;
+            const int np = pdq::wg_fan_split(stack, cap, ctl, n, fan_parts, fr + pdq::FAN_LO);
+            if (tid == 0) {
+                fr[pdq::FAN_NPARTS] = np;
+                fr[pdq::FAN_FANNED] = 1;
+                fr[pdq::FAN_TOP] = ctl.top;
+                fr[pdq::FAN_NSMALL] = ctl.nsmall;
+                __threadfence();
+                __hip_atomic_store(&fr[pdq::FAN_BOUNDS], ids_epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+#ifdef CASIM_PROF
+                if (gi < 128) {
+                    const uint64_t t_k3 = clock64();
+                    pdq::g_pdq_wg[3 * gi] = t_k3 - t_k0;
+                    pdq::g_pdq_wg[3 * gi + 1] = t_k1 - t_k0;
+                    pdq::g_pdq_wg[3 * gi + 2] = t_k3 - t_k2f;         // (fanned: spill + split)
+                }
+#endif
+            }
+            return;
+        }
+        pdq::wg_short(st, stack, cap, ctl);
 #ifdef CASIM_PROF
         const uint64_t t_k2 = clock64();
 #endif
@@ -943,12 +999,95 @@ __global__ void __launch_bounds__(pdq::NT) k_pdq_sort(const GroupMeta* __restric
         else
             for (int32_t k = tid; k < n; k += pdq::NT) sorted[off + k] = (uint32_t)e[k];
     }
-    if (ids_ready) {                                   // this group's ids are final
+    if (fan) {                                         // this group's ids are final: one part
         __syncthreads();
         if (tid == 0) {
+            int32_t* fr = fan + (size_t)gi * pdq::FAN_STRIDE;
+            fr[pdq::FAN_NPARTS] = 1;
+            fr[pdq::FAN_FANNED] = 0;
+            fr[pdq::FAN_LO] = 0;
+            fr[pdq::FAN_LO + 1] = n;
             __threadfence();
-            __hip_atomic_store(&ids_ready[gi], ids_epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(&fr[pdq::FAN_BOUNDS], ids_epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(&fr[pdq::FAN_FLAG], ids_epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
         }
+    }
+}
+
+// The second launch of the two-launch sort, queued behind k_pdq_sort on its stream (the
+// kernel boundary is the hand-off: no sort workgroup waits on another).  Workgroup (j, c)
+// finishes part j of fanned sort fmap[c]: positions [lo - 1, hi) of the spilled store back
+// into LDS at their own indices (the same dynamic LDS layout; lo - 1 is the final element
+// the partitionEqual test of a frame starting at lo reads), the pending frames inside
+// [lo, hi) into a frame area of its own, the step loop and the short frames on them, then
+// the part's ids (or positions: `sorted`, tests) and its ready flag.
+__global__ void __launch_bounds__(pdq::NT) k_pdq_sort_parts(const GroupMeta* __restrict__ groups,
+                                                           const int32_t* __restrict__ pod_idx,
+                                                           uint32_t* __restrict__ sorted, const uint64_t* __restrict__ gE,
+                                                           const pdq::Frame* __restrict__ stack_all,
+                                                           pdq::Frame* __restrict__ pstack_all, int32_t lds_n,
+                                                           const int32_t* __restrict__ fmap,
+                                                           int32_t* __restrict__ ids_out, int32_t* fan, int32_t ids_epoch) {
+    extern __shared__ __align__(16) unsigned char pdq_dyn[];
+    __shared__ pdq::Ctl ctl;
+#ifdef CASIM_PROF
+    const uint64_t t_p0 = clock64();
+#endif
+    const int gi = fmap ? fmap[blockIdx.y] : (int)blockIdx.y;
+    const int j = blockIdx.x;
+    int32_t* fr = fan + (size_t)gi * pdq::FAN_STRIDE;
+    if (!fr[pdq::FAN_FANNED] || j >= fr[pdq::FAN_NPARTS]) return;
+    const GroupMeta gm = groups[gi];
+    const int32_t n = gm.count, off = gm.off;
+    const int32_t lo = fr[pdq::FAN_LO + j], hi = fr[pdq::FAN_LO + j + 1];
+    const int tid = threadIdx.x;
+    const size_t npad = ((size_t)lds_n + 63) & ~(size_t)63;
+    uint16_t* e16 = reinterpret_cast<uint16_t*>(pdq_dyn);
+    uint8_t* rk = pdq_dyn + 2 * npad;
+    uint64_t* rmb = reinterpret_cast<uint64_t*>(pdq_dyn + 3 * npad);
+    uint16_t* rmp = reinterpret_cast<uint16_t*>(rmb + npad / 64);
+    const pdq::LdsStore st{e16, rk, rmb, rmp};
+    const uint32_t* spill = reinterpret_cast<const uint32_t*>(gE + off);
+    for (int32_t i = max(lo - 1, 0) + tid; i < hi; i += pdq::NT) st.st(i, spill[i]);
+    __syncthreads();
+#ifdef CASIM_PROF
+    const uint64_t t_p1 = clock64();
+#endif
+    pdq::Frame* stack = pstack_all + (off + lo) / 2 + 2 * (gi * pdq::FAN_PARTS_MAX + j);
+    const int cap = (hi - lo) / 2 + 2;
+    pdq::wg_fan_collect(stack_all + off / 2 + 2 * gi, n / 2 + 2, fr[pdq::FAN_TOP], fr[pdq::FAN_NSMALL], lo, hi, stack,
+                        cap, ctl);
+    pdq::wg_steps(st, n, stack, cap, (uint32_t*)nullptr, ctl, 0, 0);
+#ifdef CASIM_PROF
+    const uint64_t t_p2 = clock64();
+#endif
+    pdq::wg_short(st, stack, cap, ctl);
+#ifdef CASIM_PROF
+    const uint64_t t_p3 = clock64();
+#endif
+    if (ids_out) {
+        for (int32_t k0 = lo + tid; k0 < hi; k0 += pdq::NT * PDQ_UB) {
+            int32_t v[PDQ_UB];
+#pragma unroll
+            for (int u = 0; u < PDQ_UB; u++) { const int32_t k = k0 + u * pdq::NT; v[u] = k < hi ? pod_idx[off + (int32_t)e16[k]] : 0; }
+#pragma unroll
+            for (int u = 0; u < PDQ_UB; u++) { const int32_t k = k0 + u * pdq::NT; if (k < hi) ids_out[off + k] = v[u]; }
+        }
+    } else {
+        for (int32_t k = lo + tid; k < hi; k += pdq::NT) sorted[off + k] = e16[k];
+    }
+    __syncthreads();
+    if (tid == 0) {
+        __threadfence();
+        __hip_atomic_store(&fr[pdq::FAN_FLAG + j], ids_epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+#ifdef CASIM_PROF
+        const int slot = gi * pdq::FAN_PARTS_MAX + j;
+        if (slot < 128 * pdq::FAN_PARTS_MAX) {
+            const uint64_t t_p4 = clock64();
+            unsigned long long* w = pdq::g_pdq_part + 4 * slot;
+            w[0] = t_p1 - t_p0; w[1] = t_p2 - t_p1; w[2] = t_p3 - t_p2; w[3] = t_p4 - t_p3;
+        }
+#endif
     }
 }
 
@@ -1455,11 +1594,44 @@ __global__ void __launch_bounds__(256) k_publish(const GroupMeta* __restrict__ g
                     __builtin_amdgcn_s_sleep(2);
                 }
                 if (tk >= 0 && ids_ready) {                  // the group's Go-order ids
-                    // (the flag of the group whose sort wrote them: the group's own, or the
-                    // representative of its sort class)
-                    const int32_t g = groups[(int32_t)(uint32_t)(tk & 0xFFFFFFFFll) / nsub].ids_grp;
+                    // (the fan record of the group whose sort wrote them: the group's own, or
+                    // the representative of its sort class.)  The ticket reads Go-order
+                    // positions [s0, s1) of that sort — a pure chunk its own slice; a segment
+                    // ticket any position (single placements index the whole list), so every
+                    // part — and waits for the parts that overlap them.  The bounds are final
+                    // once FAN_BOUNDS holds this run's epoch; a flag seen up stays up, so the
+                    // flags are polled together with it (one round trip when all is ready).
+                    const int32_t tkid = (int32_t)(uint32_t)(tk & 0xFFFFFFFFll);
+                    const int32_t g0 = tkid / nsub;
+                    const int32_t* fr = ids_ready + (size_t)groups[g0].ids_grp * pdq::FAN_STRIDE;
+                    uint32_t up = 0, need = 0;
+                    bool bounds = false;
                     for (;;) {
-                        if (__hip_atomic_load(&ids_ready[g], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == ids_epoch) {
+                        int32_t fv[pdq::FAN_PARTS_MAX];
+#pragma unroll
+                        for (int j = 0; j < pdq::FAN_PARTS_MAX; j++) fv[j] = ld_coh(fr + pdq::FAN_FLAG + j);
+                        const bool bnow = bounds || ld_coh(fr + pdq::FAN_BOUNDS) == ids_epoch;
+#pragma unroll
+                        for (int j = 0; j < pdq::FAN_PARTS_MAX; j++) up |= fv[j] == ids_epoch ? 1u << j : 0u;
+                        if (bnow && !bounds) {
+                            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+                            bounds = true;
+                            int32_t lo[pdq::FAN_PARTS_MAX + 1];
+#pragma unroll
+                            for (int j = 0; j <= pdq::FAN_PARTS_MAX; j++) lo[j] = ld_coh(fr + pdq::FAN_LO + j);
+                            const int32_t np = min(ld_coh(fr + pdq::FAN_NPARTS), (int32_t)pdq::FAN_PARTS_MAX);
+                            int32_t s0 = 0, s1 = INT32_MAX;
+                            const int32_t po = (int32_t)(tk >> 32) - 1;
+                            if (po >= 0) {
+                                const int32_t a = (tkid - g0 * nsub) * pch;
+                                s0 = po + a;
+                                s1 = po + min(groups[g0].count, a + pch);
+                            }
+#pragma unroll
+                            for (int j = 0; j < pdq::FAN_PARTS_MAX; j++)
+                                if (j < np && lo[j] < s1 && lo[j + 1] > s0) need |= 1u << j;
+                        }
+                        if (bounds && (need & ~up) == 0) {
                             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
                             break;
                         }
@@ -2554,6 +2726,11 @@ struct ca_estimate_plan {
     // representatives, in group order, follow the G records of d_meta as k_pdq_sort's group
     // map — and the number of sorts the last run launched
     int32_t n_sorts = 0, ran_sorts = 0;
+    // two-launch sort (k_pdq_sort + k_pdq_sort_parts): d_ids_ready holds
+    // one fan record per group (pdqsort.h FAN_*), d_fan_map the representatives whose lists
+    // are longer than fan_min, d_pdq_pstack the part workgroups' own frame areas
+    int32_t fan_parts = 0, fan_min = 0, fan_steps = 0, n_fan = 0, ran_fan = 0;
+    DevBuf d_fan_map, d_pdq_pstack;
     hipStream_t st3 = nullptr;
     hipEvent_t ev_emitA = nullptr, ev_emitB = nullptr, ev_ids = nullptr;
     // HBM-slab rows (k_ffd_chain<true>): per group kcap and slab offset, for the limiter
@@ -3068,9 +3245,24 @@ int plan_prepare(ca_estimate_plan* p, ca_mirror* m, const ca_podset* s, const in
     if (p->decouple_ok) {
         if ((rc = p->d_sortC.reserve(sizeof(uint32_t) * tot)) != CA_OK) return rc;
         if ((rc = p->d_spod_go.reserve(sizeof(int32_t) * tot)) != CA_OK) return rc;
-        if ((rc = p->d_ids_ready.reserve(sizeof(int32_t) * (size_t)std::max(G, 1))) != CA_OK) return rc;
-        CA_HIP_CHECK(hipMemset(p->d_ids_ready.ptr, 0, sizeof(int32_t) * (size_t)std::max(G, 1)));   // epoch 0: none
+        const size_t fan_words = (size_t)pdq::FAN_STRIDE * (size_t)std::max(G, 1);
+        if ((rc = p->d_ids_ready.reserve(sizeof(int32_t) * fan_words)) != CA_OK) return rc;
+        CA_HIP_CHECK(hipMemset(p->d_ids_ready.ptr, 0, sizeof(int32_t) * fan_words));   // epoch 0: none
         p->ids_epoch = 0;
+        // Defaults from profiles/sort_fan_ab.txt; knobs are read here, once
+        fan_knobs(&p->fan_parts, &p->fan_min, &p->fan_steps);
+        std::vector<int32_t> fan_map;
+        for (int32_t g = 0; g < G && p->fan_parts > 0; g++)
+            if (p->h_meta[g].ids_grp == g && p->h_meta[g].count > p->fan_min && p->h_meta[g].count <= PDQ_LDS_N)
+                fan_map.push_back(g);
+        p->n_fan = (int32_t)fan_map.size();
+        if (p->n_fan > 0) {
+            if ((rc = p->d_fan_map.reserve(sizeof(int32_t) * fan_map.size())) != CA_OK) return rc;
+            CA_HIP_CHECK(hipMemcpy(p->d_fan_map.ptr, fan_map.data(), sizeof(int32_t) * fan_map.size(), hipMemcpyHostToDevice));
+            if ((rc = p->d_pdq_pstack.reserve(sizeof(pdq::Frame) *
+                                              (tot / 2 + 2 * (size_t)pdq::FAN_PARTS_MAX * (size_t)std::max(G, 1) + 4))) != CA_OK)
+                return rc;
+        }
         if ((rc = p->d_crank2.reserve(sizeof(int32_t) * (size_t)std::max(G, 1) * (size_t)std::max(s->n_cls, 1))) != CA_OK)
             return rc;
         if ((rc = p->d_rstart.reserve(sizeof(int32_t) * (size_t)std::max(G, 1) * (size_t)(s->n_cls + 1))) != CA_OK)
@@ -3143,13 +3335,25 @@ int launch_pdq_sort(ca_estimate_plan* p, hipStream_t ss, const int32_t* gm, int3
     const size_t lds = pdq_lds_bytes(lds_n);
     int rc;
     if ((rc = ensure_dyn_lds((const void*)k_pdq_sort, lds)) != CA_OK) return rc;
+    // the decoupled path's sorts (ids_ready: the fan table) fan out over part workgroups
+    const bool fan = ids_out && ids_ready && p->fan_parts > 0 && p->n_fan > 0;
     hipLaunchKernelGGL(k_pdq_sort, dim3(ng), dim3(pdq::NT), lds, ss, p->d_meta.as<GroupMeta>(),
                        p->d_pod_idx.as<int32_t>(), p->s ? p->s->d_cls.as<int32_t>() : nullptr, crank, U, item_rank,
                        out ? out : p->d_sortA.as<uint32_t>(), p->d_pdq_e.as<uint64_t>(), p->d_pdq_scr.as<uint64_t>(),
                        p->d_pdq_stack.as<pdq::Frame>(), lds_n, force, 0, gm, ids_out, ids_ready, ids_epoch,
                        (p->bucket && crank && !item_rank) ? p->d_item_cls.as<int32_t>() : nullptr,
-                       p->d_tmpl.as<ca_template>(), fold_np > 0 ? p->s->d_cls_sc.as<int64_t>() : nullptr, fold_np);
+                       p->d_tmpl.as<ca_template>(), fold_np > 0 ? p->s->d_cls_sc.as<int64_t>() : nullptr, fold_np,
+                       fan ? p->fan_parts : 0, p->fan_min, p->fan_steps);
     CA_HIP_CHECK(hipGetLastError());
+    if (fan) {
+        if ((rc = ensure_dyn_lds((const void*)k_pdq_sort_parts, lds)) != CA_OK) return rc;
+        hipLaunchKernelGGL(k_pdq_sort_parts, dim3(p->fan_parts, p->n_fan), dim3(pdq::NT), lds, ss,
+                           p->d_meta.as<GroupMeta>(), p->d_pod_idx.as<int32_t>(), (uint32_t*)nullptr,
+                           p->d_pdq_e.as<uint64_t>(), p->d_pdq_stack.as<pdq::Frame>(), p->d_pdq_pstack.as<pdq::Frame>(),
+                           lds_n, p->d_fan_map.as<int32_t>(), ids_out, ids_ready, ids_epoch);
+        CA_HIP_CHECK(hipGetLastError());
+    }
+    if (fan) p->ran_fan = 1;
     return CA_OK;
 }
 
@@ -3279,6 +3483,7 @@ int plan_run(ca_estimate_plan* p, const ca_limiter* lim, int32_t* last_index, ca
     const bool decoupled = go_order && p->decouple_ok && p->total > 0 &&
                            !(knob_env("CASIM_GO_DECOUPLE") && atoi(knob_env("CASIM_GO_DECOUPLE")) == 0);
     p->ran_decoupled = decoupled ? 1 : 0;
+    p->ran_fan = 0;
     p->ran_sorts = G;                                   // (decoupled: the sort classes, launch_go_sort)
     // Go's sort.Slice permutation of every group and its pod ids, on st3: its own class
     // ranks, k_pdq_sort, ids into d_spod_go and per-group ready flags holding this run's
@@ -3291,7 +3496,7 @@ int plan_run(ca_estimate_plan* p, const ca_limiter* lim, int32_t* last_index, ca
     // (the run's epoch is set before anything is queued: every consumer launched below reads it)
     if (decoupled) {
         if (p->ids_epoch == INT32_MAX) {                  // (wrapped: start over from a clean table)
-            CA_HIP_CHECK(hipMemsetAsync(p->d_ids_ready.ptr, 0, sizeof(int32_t) * (size_t)G, p->st3));
+            CA_HIP_CHECK(hipMemsetAsync(p->d_ids_ready.ptr, 0, sizeof(int32_t) * (size_t)pdq::FAN_STRIDE * (size_t)G, p->st3));
             p->ids_epoch = 0;
         }
         p->ids_epoch++;
@@ -3977,12 +4182,26 @@ int ca_estimate_plan_stats(const ca_estimate_plan* p, int32_t* rounds, float* ch
 
 int ca_estimate_plan_timings(const ca_estimate_plan* p, float* out, int32_t cap) {
     if (!p || (cap > 0 && !out)) return CA_EINVAL;
-    const int32_t n = 11;
+    const int32_t n = 12;
     for (int32_t i = 0; i < 7 && i < cap; i++) out[i] = p->t_ms[i];
     if (cap > 7) out[7] = (float)p->pub_state;
     if (cap > 8) out[8] = (float)p->ran_decoupled;
     if (cap > 9) out[9] = (float)p->ran_table_chain;
     if (cap > 10) out[10] = (float)p->ran_sorts;
+    if (cap > 11) {
+        // the parts are decided on the device: read the fan records of the run (every run is
+        // synchronised before it returns)
+        int32_t parts = p->ran_sorts;
+        if (p->ran_decoupled && p->ran_fan) {
+            const int32_t G = p->G;
+            std::vector<int32_t> rec((size_t)pdq::FAN_STRIDE * (size_t)std::max(G, 1));
+            CA_HIP_CHECK(hipMemcpy(rec.data(), p->d_ids_ready.ptr, sizeof(int32_t) * rec.size(), hipMemcpyDeviceToHost));
+            parts = 0;
+            for (int32_t g = 0; g < G; g++)
+                if (p->h_meta[g].ids_grp == g) parts += rec[(size_t)g * pdq::FAN_STRIDE + pdq::FAN_NPARTS];
+        }
+        out[11] = (float)parts;
+    }
     return n;
 }
 
@@ -4039,9 +4258,58 @@ int ca_go_sort_ranks(int32_t device, const uint32_t* ranks, int32_t n, int32_t s
     hipLaunchKernelGGL(k_pdq_sort, dim3(1), dim3(pdq::NT), lds, 0, meta.as<GroupMeta>(), nullptr, nullptr, nullptr, 0,
                        rk.as<uint32_t>(), sorted.as<uint32_t>(), e.as<uint64_t>(), scr.as<uint64_t>(),
                        stack.as<pdq::Frame>(), lds_n, store, std::max(limit, 0), nullptr, nullptr, nullptr, 0,
-                       (const int32_t*)nullptr, (const ca_template*)nullptr, (const int64_t*)nullptr, 0);
+                       (const int32_t*)nullptr, (const ca_template*)nullptr, (const int64_t*)nullptr, 0, 0, 0, 0);
     CA_HIP_CHECK(hipGetLastError());
     CA_HIP_CHECK(hipMemcpy(perm, sorted.ptr, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
+    return CA_OK;
+}
+
+int ca_go_sort_ranks_fan(int32_t device, const uint32_t* ranks, int32_t n, int32_t parts, int32_t top_steps,
+                         int32_t limit, int32_t* perm, int32_t* parts_out) {
+    if (n < 0 || n > PDQ_LDS_N || (n > 0 && (!ranks || !perm)) || parts < 1 || parts > pdq::FAN_PARTS_MAX ||
+        top_steps < 1 || top_steps > pdq::FAN_STEPS_MAX)
+        return CA_EINVAL;
+    for (int32_t i = 0; i < n; i++)
+        if (ranks[i] >= 256) return CA_EINVAL;
+    if (parts_out) *parts_out = 0;
+    if (n == 0) return CA_OK;
+    CA_HIP_CHECK(hipSetDevice(device));
+    DevBuf meta, rk, sorted, e, scr, stack, pstack, fan;
+    int rc;
+    if ((rc = meta.reserve(sizeof(GroupMeta))) != CA_OK || (rc = rk.reserve(sizeof(uint32_t) * (size_t)n)) != CA_OK ||
+        (rc = sorted.reserve(sizeof(uint32_t) * (size_t)n)) != CA_OK ||
+        (rc = e.reserve(sizeof(uint64_t) * (size_t)n)) != CA_OK || (rc = scr.reserve(sizeof(uint64_t) * (size_t)n)) != CA_OK ||
+        (rc = stack.reserve(sizeof(pdq::Frame) * ((size_t)n / 2 + 4))) != CA_OK ||
+        (rc = pstack.reserve(sizeof(pdq::Frame) * ((size_t)n / 2 + 2 * pdq::FAN_PARTS_MAX + 4))) != CA_OK ||
+        (rc = fan.reserve(sizeof(int32_t) * pdq::FAN_STRIDE)) != CA_OK)
+        return rc;
+    GroupMeta gm = {};
+    gm.off = 0;
+    gm.count = n;
+    CA_HIP_CHECK(hipMemcpy(meta.ptr, &gm, sizeof(gm), hipMemcpyHostToDevice));
+    CA_HIP_CHECK(hipMemcpy(rk.ptr, ranks, sizeof(uint32_t) * (size_t)n, hipMemcpyHostToDevice));
+    CA_HIP_CHECK(hipMemset(fan.ptr, 0, sizeof(int32_t) * pdq::FAN_STRIDE));
+    const int32_t lds_n = n;
+    const size_t lds = pdq_lds_bytes(lds_n);
+    if ((rc = ensure_dyn_lds((const void*)k_pdq_sort, lds)) != CA_OK) return rc;
+    if ((rc = ensure_dyn_lds((const void*)k_pdq_sort_parts, lds)) != CA_OK) return rc;
+    // every length fans here (fan_min -1): a root of at most T_SMALL positions is handed
+    // over as a short frame
+    hipLaunchKernelGGL(k_pdq_sort, dim3(1), dim3(pdq::NT), lds, 0, meta.as<GroupMeta>(), nullptr, nullptr, nullptr, 0,
+                       rk.as<uint32_t>(), sorted.as<uint32_t>(), e.as<uint64_t>(), scr.as<uint64_t>(),
+                       stack.as<pdq::Frame>(), lds_n, 1, std::max(limit, 0), nullptr, nullptr, fan.as<int32_t>(), 1,
+                       (const int32_t*)nullptr, (const ca_template*)nullptr, (const int64_t*)nullptr, 0, parts, -1,
+                       top_steps);
+    CA_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(k_pdq_sort_parts, dim3(parts, 1), dim3(pdq::NT), lds, 0, meta.as<GroupMeta>(), nullptr,
+                       sorted.as<uint32_t>(), e.as<uint64_t>(), stack.as<pdq::Frame>(), pstack.as<pdq::Frame>(), lds_n,
+                       (const int32_t*)nullptr, (int32_t*)nullptr, fan.as<int32_t>(), 1);
+    CA_HIP_CHECK(hipGetLastError());
+    CA_HIP_CHECK(hipMemcpy(perm, sorted.ptr, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
+    int32_t rec[pdq::FAN_STRIDE];
+    CA_HIP_CHECK(hipMemcpy(rec, fan.ptr, sizeof(rec), hipMemcpyDeviceToHost));
+    if (!rec[pdq::FAN_FANNED]) return CA_EINVAL;        // (not the LDS store: cannot happen for ranks < 256)
+    if (parts_out) *parts_out = rec[pdq::FAN_NPARTS];
     return CA_OK;
 }
 
@@ -4055,6 +4323,17 @@ int ca_debug_pdq_prof(uint64_t* out, int32_t reset) {
         CA_HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(pdq::g_pdq_prof), z, sizeof z));
         CA_HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(pdq::g_pdq_pis), z, sizeof(uint64_t) * 8));
     }
+    return CA_OK;
+}
+
+// two-launch sort: out[3 g + k] = k_pdq_sort's workgroup of group g (kernel, prologue, spill +
+// split cycles), then out[384 + 4 (16 g + j) + k] = part j of group g in k_pdq_sort_parts
+// (load, steps, short frames, ids out); 384 + 8192 words, the parts' zeroed after the copy
+int ca_debug_pdq_fan_prof(uint64_t* out) {
+    CA_HIP_CHECK(hipMemcpyFromSymbol(out, HIP_SYMBOL(pdq::g_pdq_wg), sizeof(uint64_t) * 3 * 128));
+    CA_HIP_CHECK(hipMemcpyFromSymbol(out + 3 * 128, HIP_SYMBOL(pdq::g_pdq_part), sizeof(uint64_t) * 4 * 128 * 16));
+    static const uint64_t z[4 * 128 * 16] = {};
+    CA_HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(pdq::g_pdq_part), z, sizeof z));
     return CA_OK;
 }
 

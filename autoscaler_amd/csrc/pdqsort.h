@@ -49,6 +49,8 @@ __device__ unsigned long long g_pdq_pis[8];
 // per workgroup (group slot < 128): kernel cycles, prologue (ranks into the store) cycles,
 // epilogue (ids out) cycles
 __device__ unsigned long long g_pdq_wg[3 * 128];
+// two-launch sort, per part workgroup (slot 16 group + part): load, steps, short frames, ids out
+__device__ unsigned long long g_pdq_part[4 * 128 * 16];
 #define PDQ_PIS(k, v) do { if ((threadIdx.x & 63) == 0 && blockIdx.x == 0) atomicAdd(&g_pdq_pis[k], (unsigned long long)(v)); } while (0)
 #define PDQ_S(k, v) do { if (threadIdx.x == 0 && blockIdx.x == 0 && g_pdq_step < 16) g_pdq_prof[32 + 16 * g_pdq_step + (k)] += (unsigned long long)(v); } while (0)
 #define PDQ_SMAXW(k, v) do { if ((threadIdx.x & 63) == 0 && blockIdx.x == 0 && g_pdq_step < 16) atomicMax(&g_pdq_prof[32 + 16 * g_pdq_step + (k)], (unsigned long long)(v)); } while (0)
@@ -1529,11 +1531,11 @@ __device__ bool w_partial_insertion(const LdsStore& s, int a, int b, int pi = -1
 // T_SMALL grow from its start, shorter ones from its end (they are sorted last, one
 // wavefront each, with no workgroup barrier).  xs: n elements of exchange scratch.
 // limit0 > 0 replaces sort.Slice's initial limit bits.Len(n) (tests: the heapSort fallback).
-template <class S> __device__ void wg_sort(const S& s, int n, Frame* __restrict__ stack, int cap,
-                                           typename S::Elem* __restrict__ xs, Ctl& c, int limit0) {
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    PDQ_T(t_all);
-    if (tid == 0) {
+// Three pieces, shared by every store and by both kernels of the two-launch sort:
+// wg_sort_root pushes the root call, wg_steps runs workgroup steps until no long frame is
+// pending or a stop rule holds, wg_short sorts the short frames.
+template <class S> __device__ __forceinline__ void wg_sort_root(int n, Frame* __restrict__ stack, int cap, Ctl& c, int limit0) {
+    if (threadIdx.x == 0) {
         c.top = 0;
         c.nsmall = 0;
         c.snext = 0;
@@ -1543,6 +1545,17 @@ template <class S> __device__ void wg_sort(const S& s, int n, Frame* __restrict_
             else { stack[0] = root; c.top = 1; }
         }
     }
+    __syncthreads();
+}
+
+// Workgroup steps on the long frames stack[0, c.top).  stop_parts > 0 (the top phase of
+// the two-launch sort): return after the step that leaves at least stop_parts long frames
+// pending, or after stop_steps steps; the pending frames stay in stack (c.top long ones,
+// c.nsmall short ones).  stop_parts == 0: until no long frame is pending.
+template <class S> __device__ __forceinline__ void wg_steps(const S& s, int n, Frame* __restrict__ stack, int cap,
+                                            typename S::Elem* __restrict__ xs, Ctl& c, int stop_parts, int stop_steps) {
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    int steps = 0;
 #ifdef CASIM_PROF
     if (tid == 0 && blockIdx.x == 0) g_pdq_step = -1;
 #endif
@@ -1553,7 +1566,8 @@ template <class S> __device__ void wg_sort(const S& s, int n, Frame* __restrict_
 #endif
         PDQ_T(t_pop);
         if (tid == 0) {
-            const int nf = min(c.top, MAXF);
+            const bool stop = stop_parts > 0 && steps > 0 && (c.top >= stop_parts || steps >= stop_steps);
+            const int nf = stop ? 0 : min(c.top, MAXF);
             c.nf = nf;
             c.top -= nf;
             c.base = c.top;
@@ -1561,6 +1575,7 @@ template <class S> __device__ void wg_sort(const S& s, int n, Frame* __restrict_
         __syncthreads();
         const int nf = c.nf;
         if (nf == 0) break;
+        steps++;
         for (int i = tid; i < nf; i += NT) {
             c.f[i] = stack[c.base + i];
             c.op[i] = OP_DONE;
@@ -1733,7 +1748,11 @@ template <class S> __device__ void wg_sort(const S& s, int n, Frame* __restrict_
         PDQ_ADD(9, t_d);
         PDQ_S(9, clock64() - t_d);
     }
-    // the short frames, one wavefront each, claimed in turn
+}
+
+// the short frames stack[cap - 1 - q], q < c.nsmall: one wavefront each, claimed in turn
+template <class S> __device__ __forceinline__ void wg_short(const S& s, Frame* __restrict__ stack, int cap, Ctl& c) {
+    const int lane = threadIdx.x & 63;
     PDQ_T(t_small);
     const int ns = c.nsmall;
     PDQ_CNT(14, ns);
@@ -1748,7 +1767,98 @@ template <class S> __device__ void wg_sort(const S& s, int n, Frame* __restrict_
     __threadfence_block();
     __syncthreads();
     PDQ_ADD(10, t_small);
+}
+
+template <class S> __device__ __forceinline__ void wg_sort(const S& s, int n, Frame* __restrict__ stack, int cap,
+                                           typename S::Elem* __restrict__ xs, Ctl& c, int limit0) {
+    PDQ_T(t_all);
+    wg_sort_root<S>(n, stack, cap, c, limit0);
+    wg_steps(s, n, stack, cap, xs, c, 0, 0);
+    wg_short(s, stack, cap, c);
     PDQ_ADD(0, t_all);
+}
+
+// ---------------------------------------------------------------------------------
+// two-launch sort (LDS store): the hand-off between the top phase and the part workgroups
+// ---------------------------------------------------------------------------------
+// The top phase stops with c.top long and c.nsmall short frames pending in `stack`, at most
+// 2^FAN_STEPS_MAX of them (a step leaves at most two frames per frame it ran).  The part
+// workgroups of the next launch each take the frames inside one contiguous range of
+// positions.  A sort's record in the fan table (int32 words):
+constexpr int FAN_PARTS_MAX = 16;
+constexpr int FAN_STEPS_MAX = 8;
+enum {
+    FAN_FLAG = 0,                          // [j]: the run epoch whose ids of part j are final
+    FAN_BOUNDS = FAN_PARTS_MAX,            // the run epoch whose NPARTS / LO are final
+    FAN_NPARTS = FAN_PARTS_MAX + 1,        // parts of this run (1: the sort ended in the first launch)
+    FAN_FANNED = FAN_PARTS_MAX + 2,        // 1: the part workgroups finish this sort
+    FAN_TOP = FAN_PARTS_MAX + 3,           // pending long / short frames at the hand-off
+    FAN_NSMALL = FAN_PARTS_MAX + 4,
+    FAN_LO = FAN_PARTS_MAX + 5,            // [0 .. NPARTS]: part j is positions [LO[j], LO[j+1])
+    FAN_STRIDE = 2 * FAN_PARTS_MAX + 8,
+};
+
+__device__ __forceinline__ Frame fan_frame(const Frame* __restrict__ stack, int cap, int nl, int t) {
+    return t < nl ? stack[t] : stack[cap - 1 - (t - nl)];
+}
+
+// [0, n) into at most `parts` ranges cut at frame starts only (the element left of a frame
+// is final, so is everything between frames), balanced by the summed length of the frames
+// in each: with the frames laid end to end in position order, a frame goes to the part its
+// midpoint falls in (parts equal shares of the summed length), and a part starts at its
+// first frame; shares that receive no frame give no part.  Two pending frames' midpoints
+// are at least half the sum apart, so two or more frames give two or more parts.
+// lo[0 .. return value] receives the bounds.
+__device__ __forceinline__ int wg_fan_split(const Frame* __restrict__ stack, int cap, Ctl& c, int n, int parts, int32_t* lo) {
+    static_assert(FAN_PARTS_MAX <= MAXF, "the parts' first frame starts live in Ctl::po between steps");
+    const int tid = threadIdx.x;
+    const int nl = c.top, F = c.top + c.nsmall;
+    if (tid < FAN_PARTS_MAX) c.po[tid] = INT_MAX;
+    __syncthreads();
+    for (int t = tid; t < F; t += NT) {
+        const Frame mine = fan_frame(stack, cap, nl, t);
+        int64_t before = 0, total = 0;
+        for (int u = 0; u < F; u++) {
+            const Frame f = fan_frame(stack, cap, nl, u);
+            total += f.b - f.a;
+            if (f.a < mine.a) before += f.b - f.a;
+        }
+        const int share = (int)min((int64_t)(parts - 1), (2 * before + (mine.b - mine.a)) * parts / (2 * total));
+        atomicMin(&c.po[share], mine.a);
+    }
+    __syncthreads();
+    if (tid == 0) {
+        int k = 0;
+        bool first = true;                 // (the first part starts at 0, not at its first frame)
+        lo[0] = 0;
+        for (int j = 0; j < parts; j++) {
+            const int v = c.po[j];
+            if (v == INT_MAX) continue;
+            if (!first) lo[++k] = v;
+            first = false;
+        }
+        lo[++k] = n;
+        c.x0 = k;
+    }
+    __syncthreads();
+    return c.x0;
+}
+
+// the pending frames inside [lo, hi) into a part's own frame area (long ones from its
+// start, short ones from its end, as wg_steps / wg_short expect them)
+__device__ __forceinline__ void wg_fan_collect(const Frame* __restrict__ src, int src_cap, int nl, int ns, int lo, int hi,
+                                      Frame* __restrict__ stack, int cap, Ctl& c) {
+    const int tid = threadIdx.x;
+    if (tid == 0) { c.top = 0; c.nsmall = 0; c.snext = 0; }
+    __syncthreads();
+    for (int t = tid; t < nl + ns; t += NT) {
+        const Frame f = fan_frame(src, src_cap, nl, t);
+        if (f.a < lo || f.b > hi) continue;
+        if (t < nl) stack[atomicAdd(&c.top, 1)] = f;
+        else stack[cap - 1 - atomicAdd(&c.nsmall, 1)] = f;
+    }
+    __threadfence_block();
+    __syncthreads();
 }
 
 }  // namespace pdq

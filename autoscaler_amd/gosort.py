@@ -14,8 +14,11 @@ from __future__ import annotations
 from typing import Callable, Sequence
 
 
-def sort_slice(n: int, less: Callable[[int, int], bool], swap: Callable[[int, int], None]) -> None:
-    """sort.Slice over an abstract sequence of length n (Less / Swap by index)."""
+def sort_slice(n: int, less: Callable[[int, int], bool], swap: Callable[[int, int], None],
+               on_iteration: Callable[[int, int, int], None] = None) -> None:
+    """sort.Slice over an abstract sequence of length n (Less / Swap by index).
+    on_iteration(a, b, level) is called at the start of every pdqsort_func loop iteration:
+    level counts the iterations between it and the root call (see pending_frames)."""
 
     def insertion_sort(a, b):
         for i in range(a + 1, b):
@@ -153,9 +156,13 @@ def sort_slice(n: int, less: Callable[[int, int], bool], swap: Callable[[int, in
             j -= 1
         return i
 
-    def pdqsort(a, b, limit):
+    def pdqsort(a, b, limit, level=0):
         was_balanced, was_partitioned = True, True
+        level -= 1
         while True:
+            level += 1
+            if on_iteration is not None:
+                on_iteration(a, b, level)
             length = b - a
             if length <= 12:
                 insertion_sort(a, b)
@@ -186,11 +193,11 @@ def sort_slice(n: int, less: Callable[[int, int], bool], swap: Callable[[int, in
             threshold = length // 8
             if left < right:
                 was_balanced = left >= threshold
-                pdqsort(a, mid, limit)
+                pdqsort(a, mid, limit, level + 1)
                 a = mid + 1
             else:
                 was_balanced = right >= threshold
-                pdqsort(mid + 1, b, limit)
+                pdqsort(mid + 1, b, limit, level + 1)
                 b = mid
 
     pdqsort(0, n, n.bit_length())
@@ -210,3 +217,39 @@ def sort_slice_desc(keys: Sequence) -> list:
 
     sort_slice(len(perm), less, swap)
     return perm
+
+
+def pending_frames(ranks: Sequence, parts: int, top_steps: int, t_small: int = 2048) -> tuple:
+    """The device's two-launch sort (csrc/pdqsort.h) runs the iterations of one level per
+    workgroup step, on the frames longer than t_small only, and hands over after the first
+    step that leaves at least `parts` such frames pending, or after `top_steps` steps.
+    Returns (long, short): the frames of two or more positions pending at that hand-off for
+    less(i, j) == ranks[i] < ranks[j].  Frames are independent of each other, so the
+    depth-first order here meets the same frames at the same levels."""
+    perm = list(range(len(ranks)))
+    k = list(ranks)
+    calls = []
+
+    def less(i, j):
+        return k[perm[i]] < k[perm[j]]
+
+    def swap(i, j):
+        perm[i], perm[j] = perm[j], perm[i]
+
+    def note(a, b, level):
+        if b - a >= 2:
+            calls.append((level, a, b))
+
+    sort_slice(len(perm), less, swap, note)
+    long_at = lambda s: [(a, b) for (lv, a, b) in calls if lv == s and b - a > t_small]
+    stop = 0
+    if long_at(0):
+        stop = 1
+        while long_at(stop) and len(long_at(stop)) < parts and stop < top_steps:
+            stop += 1
+    # a short frame is pending when its parent was long: it is inside no shorter-level short frame
+    short = []
+    for lv, a, b in sorted(calls):
+        if lv <= stop and b - a <= t_small and not any(x <= a and b <= y for x, y in short):
+            short.append((a, b))
+    return long_at(stop), short

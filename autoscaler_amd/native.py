@@ -100,6 +100,7 @@ def load() -> C.CDLL:
         "ca_estimate_plan_chain_info": ([vp, p(i32), p(i32)], C.c_int),
         "ca_estimate_plan_rebase": ([vp, vp, i32, p(i32)], C.c_int),
         "ca_go_sort_ranks": ([i32, vp, i32, i32, i32, vp], C.c_int),
+        "ca_go_sort_ranks_fan": ([i32, vp, i32, i32, i32, i32, vp, p(i32)], C.c_int),
         "ca_estimate_plan_timings": ([vp, p(C.c_float), i32], C.c_int),
         "ca_estimate_plan_set_phase_timing": ([vp, i32], C.c_int),
         "ca_estimate_plan_group_ticks": ([vp, p(C.c_uint64), i32], C.c_int),
@@ -213,7 +214,7 @@ def exported_symbols() -> list[str]:
         "ca_estimate_plan_option_sums", "ca_estimate_plan_option_sums_ms", "ca_estimate_plan_fetch_group",
         "ca_expander_best_options", "ca_estimate_plan_option_price_sums", "ca_estimate_plan_option_price_sums_ms",
         "ca_estimate_plan_groups_missing_pods", "ca_estimate_plan_groups_missing_pods_ms",
-        "ca_go_sort_ranks",
+        "ca_go_sort_ranks", "ca_go_sort_ranks_fan",
         "ca_find_nodes_to_remove",
         "ca_removal_stats", "ca_removal_timings", "ca_removal_plan_create", "ca_removal_plan_run",
         "ca_removal_plan_destroy", "ca_removal_plan_sensitive_pods", "ca_removal_plan_phased",
@@ -243,6 +244,19 @@ def go_sort_ranks(ranks, store: int = 0, limit: int = 0, device: int = 0) -> np.
     if st != abi.CA_OK:
         raise CasimError(st, "go_sort_ranks")
     return perm[: len(r)]
+
+
+def go_sort_ranks_fan(ranks, parts: int = 8, top_steps: int = 4, limit: int = 0, device: int = 0) -> tuple:
+    """The same permutation through the two-launch LDS-store sort (ca_go_sort_ranks_fan):
+    (perm, number of parts the split produced)."""
+    r = np.ascontiguousarray(ranks, dtype=np.uint32)
+    perm = np.zeros(max(len(r), 1), np.int32)
+    n_parts = C.c_int32(0)
+    st = load().ca_go_sort_ranks_fan(device, r.ctypes.data, len(r), parts, top_steps, limit, perm.ctypes.data,
+                                     C.byref(n_parts))
+    if st != abi.CA_OK:
+        raise CasimError(st, "go_sort_ranks_fan")
+    return perm[: len(r)], n_parts.value
 
 
 def sweep_compose(recs: np.ndarray, n_nodes: int, last_index: int) -> np.ndarray:
@@ -963,14 +977,15 @@ class EstimatePlan:
         self.lib.ca_estimate_plan_stats(self.h, C.byref(r), C.byref(a), C.byref(b), C.byref(c))
         sens, succ = C.c_int32(0), C.c_int32(0)
         self.lib.ca_estimate_plan_chain_info(self.h, C.byref(sens), C.byref(succ))
-        t = (C.c_float * 11)()
-        self.lib.ca_estimate_plan_timings(self.h, t, 11)
+        t = (C.c_float * 12)()
+        self.lib.ca_estimate_plan_timings(self.h, t, 12)
         names = ("score_ms", "merge_ms", "emit_ms", "chain_ms", "compact_ms", "d2h_ms", "host_ms")
         return {"rounds": r.value, "chain_ms": a.value, "sort_ms": b.value, "total_ms": c.value,
                 "lin_sensitive": sens.value, "had_success": succ.value,
                 "phases": {k: float(v) for k, v in zip(names, t)},
                 "results_path": ("copied", "published", "publisher_gave_up")[int(t[7])],
-                "decoupled": bool(t[8]), "table_chain": bool(t[9]), "sorts": int(t[10])}
+                "decoupled": bool(t[8]), "table_chain": bool(t[9]), "sorts": int(t[10]),
+                "sort_parts": int(t[11])}
 
     def set_phase_timing(self, on: bool) -> None:
         """Per-phase timing events on later runs (on by default; off keeps them off the

@@ -404,6 +404,14 @@ int ca_estimate_batch(ca_mirror* m, const ca_podset* s,
  * and Go-side checks. */
 int ca_go_sort_ranks(int32_t device, const uint32_t* ranks, int32_t n, int32_t store, int32_t limit,
                      int32_t* perm);
+/* The same permutation through the two-launch form of the LDS-store sort that the
+ * decoupled Estimate path uses for long lists: the first kernel stops after the workgroup
+ * step that leaves `parts` long frames pending (top_steps steps at most), up to `parts`
+ * workgroups of the second finish one range of positions each.  n <= 50368 and ranks
+ * < 256 (1 <= parts <= 16, 1 <= top_steps <= 8), else CA_EINVAL.  parts_out: the ranges
+ * the split produced.  For tests. */
+int ca_go_sort_ranks_fan(int32_t device, const uint32_t* ranks, int32_t n, int32_t parts, int32_t top_steps,
+                         int32_t limit, int32_t* perm, int32_t* parts_out);
 
 /* Prepared form for repeated calls (bench): uploads group lists/templates once. */
 typedef struct ca_estimate_plan ca_estimate_plan;
@@ -440,8 +448,10 @@ int ca_estimate_plan_stats(const ca_estimate_plan* p, int32_t* rounds, float* ch
  * the podset's score classes fits the chain's LDS beside its rows), else 0 — the chains
  * read the emitted stream; [10] the Go-order sorts the run launched: groups with equal pod
  * lists whose templates rank the podset's score classes alike share one on the decoupled
- * path (CASIM_SORT_SHARE=0: one per group), otherwise the number of groups.  Writes
- * min(cap, 11) values; returns 11. */
+ * path (CASIM_SORT_SHARE=0: one per group), otherwise the number of groups; [11] the
+ * parts those sorts' ids were finished and flagged in: a long list's sort fans out over
+ * several workgroups of a second launch (CASIM_SORT_FAN=0: never), every other sort is one
+ * part, so [11] == [10] when nothing fanned.  Writes min(cap, 12) values; returns 12. */
 int ca_estimate_plan_timings(const ca_estimate_plan* p, float* out, int32_t cap);
 /* Record the per-phase timing events of later runs (on: default) or not: 8 event records
  * per run on the host's launch path; with them off, ca_estimate_plan_timings[0..5] and the
