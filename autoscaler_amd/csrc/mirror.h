@@ -259,6 +259,10 @@ struct ca_mirror {
     std::vector<uint8_t> dirty_flag;
     bool static_dirty = true;              // static/ext columns need a full upload
     bool all_dirty = true;
+    // ca_mirror_sync_stats: counters since create / Clear() (casim.h has the order)
+    enum { SS_FULL = 0, SS_STAGED, SS_ROWS_STAGED, SS_STATIC, SS_GROWTHS, SS_DEVICE_ROWS, SS_FILL_THREADS,
+           SS_PLACED_THREADS, SS_N };
+    int64_t sync_stat[SS_N] = {0};
 
     // device pod table (mirror pods), appended lazily
     casim::DevPodTable d_pods;

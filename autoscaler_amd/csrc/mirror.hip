@@ -502,6 +502,7 @@ void ca_mirror::add_placed_batch(const ca_pod_table* t, const int32_t* idx, cons
     tmark("reserved");
     int32_t T = plain ? std::min(8, np / 2048) : 1;
     T = T >= 8 ? 8 : T >= 4 ? 4 : T >= 2 ? 2 : 1;              // (a power of two: 64-node block & (T - 1) picks the thread)
+    sync_stat[SS_PLACED_THREADS] = T;
     const int32_t tmask = T - 1;
     // rows dirty before this batch stay dirty; the batch's own marks are dropped below where
     // the kernel's row equals fill_hot's
@@ -517,6 +518,7 @@ void ca_mirror::add_placed_batch(const ca_pod_table* t, const int32_t* idx, cons
             if (fp >= INT32_MIN && fp + np <= INT32_MAX && (size_t)x < d_rows) { dirty_flag[x] = 0; continue; }
             dirty_rows[w++] = x;
         }
+        sync_stat[SS_DEVICE_ROWS] += (int64_t)(dirty_rows.size() - w);
         dirty_rows.resize(w);
     };
     if (T <= 1) {
@@ -550,7 +552,7 @@ void ca_mirror::add_placed_batch(const ca_pod_table* t, const int32_t* idx, cons
     tmark("resized");
     struct Part {
         std::vector<int32_t> dirty;
-        int64_t ext = 0, eph = 0, blockers = 0, oos = 0;
+        int64_t ext = 0, eph = 0, blockers = 0, oos = 0, device_rows = 0;
     };
     std::vector<Part> part((size_t)T);
     const bool journaled = depth > 0;
@@ -608,6 +610,7 @@ void ca_mirror::add_placed_batch(const ca_pod_table* t, const int32_t* idx, cons
                 if (fp >= INT32_MIN && fp + np <= INT32_MAX && (size_t)x < d_rows) { dirty_flag[x] = 0; continue; }
                 pt.dirty[o++] = x;
             }
+            pt.device_rows = (int64_t)(pt.dirty.size() - o);
             pt.dirty.resize(o);
         }
         if (dbg_t) tw[3 * w + 2] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -623,6 +626,7 @@ void ca_mirror::add_placed_batch(const ca_pod_table* t, const int32_t* idx, cons
         n_eph_pods += pt.eph;
         n_oos_pods += pt.oos;
         n_scope_blockers += pt.blockers;
+        sync_stat[SS_DEVICE_ROWS] += pt.device_rows;
         dirty_rows.insert(dirty_rows.end(), pt.dirty.begin(), pt.dirty.end());
     }
     if (out_id)
@@ -720,6 +724,7 @@ int ca_mirror::sync_nodes() {
         if ((rc = d_ext.reserve(sizeof(NodeExt) * cap)) != CA_OK) return rc;
         if ((rc = d_static.reserve(sizeof(NodeStatic) * cap)) != CA_OK) return rc;
         d_cap = cap;
+        sync_stat[SS_GROWTHS]++;
         all_dirty = true;
         static_dirty = true;
     }
@@ -735,6 +740,8 @@ int ca_mirror::sync_nodes() {
         NodeExt* e = reinterpret_cast<NodeExt*>(h + n);
         // (a revert's or a new snapshot's thousands of rows: filled by the host workers)
         const int32_t T = (int32_t)std::max<size_t>(1, std::min<size_t>(8, n / 2048));
+        sync_stat[SS_FULL]++;
+        sync_stat[SS_FILL_THREADS] = T;
         casim::parallel_run(T, [&](int32_t w) {
             const size_t i0 = n * (size_t)w / (size_t)T, i1 = n * (size_t)(w + 1) / (size_t)T;
             for (size_t i = i0; i < i1; i++) { fill_hot((int32_t)i, h[i]); fill_ext((int32_t)i, e[i]); }
@@ -754,6 +761,8 @@ int ca_mirror::sync_nodes() {
         // few rows: stage them (row id + both columns) in pinned memory, one H2D copy, and
         // scatter them on the device
         const size_t k = dirty_rows.size();
+        sync_stat[SS_STAGED]++;
+        sync_stat[SS_ROWS_STAGED] += (int64_t)k;
         const size_t kcap = std::max<size_t>(k, std::max<size_t>(64, n / 4));   // the largest staged batch
         if ((rc = rs.h.reserve(sizeof(StagedRow) * kcap)) != CA_OK) return rc;
         if ((rc = rs.d.reserve(sizeof(StagedRow) * kcap)) != CA_OK) return rc;
@@ -776,6 +785,7 @@ int ca_mirror::sync_nodes() {
         CA_HIP_CHECK(hipStreamSynchronize(stream));        // the staging buffer is reused
     }
     if (static_dirty && n) {
+        sync_stat[SS_STATIC]++;
         std::vector<NodeStatic> s(n);
         const int32_t T = (int32_t)std::max<size_t>(1, std::min<size_t>(8, n / 2048));
         casim::parallel_run(T, [&](int32_t w) {
@@ -1080,6 +1090,7 @@ int ca_mirror_clear(ca_mirror* m) {
     m->all_dirty = true; m->static_dirty = true; m->d_rows = 0;
     m->d_pods_synced = 0; m->d_terms_synced = 0;
     m->d_hints_n = 0;
+    for (int64_t& c : m->sync_stat) c = 0;
     return CA_OK;
 }
 
@@ -1195,6 +1206,12 @@ int ca_mirror_scope_blockers(const ca_mirror* m, int32_t* out_n) {
     return CA_OK;
 }
 
+int ca_mirror_sync_stats(const ca_mirror* m, int64_t* out, int32_t cap) {
+    if (!m || (!out && cap > 0)) return CA_EINVAL;
+    for (int32_t i = 0; i < cap && i < ca_mirror::SS_N; i++) out[i] = m->sync_stat[i];
+    return ca_mirror::SS_N;
+}
+
 int ca_mirror_fork(ca_mirror* m) {
     if (!m) return CA_EINVAL;
     m->depth++;
@@ -1226,8 +1243,12 @@ int ca_mirror_revert(ca_mirror* m) {
             NodeRow& nd = m->nodes[e.node];
             m->node_apply(e.node, m->pods[e.pod].spec, +1);
             std::memcpy(nd.ports, e.ports, sizeof e.ports);
-            nd.pods.push_back(nd.pods[e.slot]);
-            nd.pods[e.slot] = e.pod;
+            if ((size_t)e.slot == nd.pods.size()) {           // the pod was last in its list
+                nd.pods.push_back(e.pod);
+            } else {
+                nd.pods.push_back(nd.pods[e.slot]);
+                nd.pods[e.slot] = e.pod;
+            }
             m->pods[e.pod].node = e.node;
         } else if (e.kind == J_REMOVE_NODE) {
             const int32_t pos = e.node;

@@ -123,6 +123,7 @@ def load() -> C.CDLL:
         "ca_sweep_compose": ([vp, i32, i32, i32, vp, p(i32)], C.c_int),
         "ca_mirror_set_hints": ([vp, vp, i32], C.c_int),
         "ca_mirror_get_hints": ([vp, vp, i32], C.c_int),
+        "ca_mirror_sync_stats": ([vp, p(C.c_int64), i32], C.c_int),
         "ca_removal_candidate_ticks": ([vp, p(C.c_uint64), i32], C.c_int),
         "ca_removal_timings": ([vp, p(C.c_float), i32], C.c_int),
         "ca_filter_out_schedulable": ([vp, vp, vp, vp, i32, vp, i32, vp, p(i32), vp, vp, p(i32), p(C.c_uint64), p(i32)],
@@ -219,6 +220,7 @@ def exported_symbols() -> list[str]:
         "ca_removal_stats", "ca_removal_timings", "ca_removal_plan_create", "ca_removal_plan_run",
         "ca_removal_plan_destroy", "ca_removal_plan_sensitive_pods", "ca_removal_plan_phased",
         "ca_removal_plan_run_phase", "ca_sweep_compose", "ca_mirror_set_hints", "ca_mirror_get_hints",
+        "ca_mirror_sync_stats",
         "ca_removal_candidate_ticks", "ca_filter_out_schedulable", "ca_try_schedule_pods", "ca_filter_stats",
         "ca_util_table_create", "ca_util_table_destroy", "ca_util_calculate", "ca_util_device_results",
         "ca_util_table_update", "ca_util_table_set_added", "ca_multi_create", "ca_multi_destroy",
@@ -672,6 +674,14 @@ class Mirror:
         h = np.zeros(n_pods, np.int32)
         _check(self.lib.ca_mirror_get_hints(self.h, ptr(h), n_pods), "ca_mirror_get_hints")
         return h
+
+    def sync_stats(self) -> dict:
+        """How the device rows were brought up to date since create / clear (ca_mirror_sync_stats)."""
+        out = (C.c_int64 * 8)()
+        self.lib.ca_mirror_sync_stats(self.h, out, 8)
+        names = ["full_syncs", "staged_syncs", "rows_staged", "static_uploads", "growths", "device_rows",
+                 "fill_threads", "placed_threads"]
+        return {nm: int(v) for nm, v in zip(names, out)}
 
     def candidate_ticks(self, n_candidates: int) -> np.ndarray:
         """Per candidate of the last sweep: device time of its simulation, us."""

@@ -589,6 +589,14 @@ int ca_removal_plan_run(ca_removal_plan* p, int32_t* hints, int32_t* last_index,
 int ca_removal_plan_destroy(ca_removal_plan* p);
 int ca_mirror_set_hints(ca_mirror* m, const int32_t* hints, int32_t n_pods);
 int ca_mirror_get_hints(ca_mirror* m, int32_t* hints, int32_t n_pods);
+/* Diagnostics (read-only): how the mirror brought its device rows up to date since
+ * ca_mirror_create or the last ca_mirror_clear.  out[0] full-table row uploads, [1] staged
+ * uploads (dirty rows scattered by a kernel), [2] rows staged in total, [3] uploads of the
+ * static column, [4] growths of the device row buffers, [5] rows a placement batch took off
+ * the dirty list because the caller's kernel had already written them on the device, [6] host
+ * threads of the last full-table fill, [7] host threads of the last placement batch
+ * (FilterOutSchedulable / TrySchedulePods commits); returns 8. */
+int ca_mirror_sync_stats(const ca_mirror* m, int64_t* out, int32_t cap);
 int ca_removal_timings(const ca_mirror* m, float* out, int32_t cap);
 int ca_removal_stats(const ca_mirror* m, int32_t* rounds, float* kernel_ms, float* total_ms);
 /* Diagnostics: device wall-clock ticks (100 MHz) each candidate's simulation took in the

@@ -845,6 +845,7 @@ def test_fork_revert_commit_parity(oracle):
     for step in range(60):
         op = rng.choice(["fork", "add", "add", "revert", "commit", "fits"])
         ops.append(op)
+        raised = []
         for s, t in ((so, to), (sg, tg)):
             b = s.backend
             if op == "fork":
@@ -854,8 +855,11 @@ def test_fork_revert_commit_parity(oracle):
             elif op in ("revert", "commit"):
                 try:
                     getattr(b, op)()
-                except Exception:
-                    pass
+                    raised.append(None)
+                except (oracle.OracleError, native.CasimError) as e:
+                    raised.append(e.status)
+        # both raise, or neither (CA_ESTATE outside a fork), on the same steps
+        assert len(set(raised)) <= 1, (ops, raised)
         if op == "fits":
             assert so.backend.fits_any_node(to, step % len(pending), None, step) == \
                 sg.backend.fits_any_node(tg, step % len(pending), None, step), ops
