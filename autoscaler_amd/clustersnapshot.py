@@ -59,6 +59,10 @@ class _State:
         del self.nodes[name]
         del self.pods[name]
 
+    def set_order(self, names: list) -> None:
+        self.names = list(names)
+        self.pos = {n: i for i, n in enumerate(self.names)}
+
     def remove_pod(self, ns: str, name: str, node: str) -> int:
         lst = self.pods[node]
         for i, (p, pid) in enumerate(lst):
@@ -123,6 +127,9 @@ class ClusterSnapshot:
             pos = st.pos[op[1]]
             self.backend.remove_node(pos)
             st.remove_node(op[1])
+        elif kind == "order":
+            self.backend.reorder_nodes([st.pos[n] for n in op[1]])
+            st.set_order(op[1])
         elif kind == "fork":
             self._stack.append(copy.deepcopy(st))
             self.backend.fork()
@@ -160,6 +167,26 @@ class ClusterSnapshot:
         if node_name not in self._state.pos:
             raise NodeNotFoundError(node_name)
         self._apply(("rmnode", node_name))
+
+    def SetNodeOrder(self, names: list) -> None:  # noqa: N802
+        """The node list in the order the reference's NodeInfos().List() now returns it (it is
+        rebuilt from a Go map after an unforked mutation): `names` are exactly
+        the current node names.  Pods, their NodeInfo.Pods order and resident hints follow
+        their node.  Not inside a fork (the mirror's journal holds positions)."""
+        names = list(names)
+        st = self._state
+        if self._stack:
+            raise RuntimeError("SetNodeOrder inside a fork")
+        if len(names) != len(st.names) or set(names) != set(st.names):
+            raise ValueError("SetNodeOrder: names are not the snapshot's node names")
+        if hasattr(self.backend, "reorder_nodes"):
+            self._apply(("order", names))
+            return
+        # a backend without the call: the log in canonical form (the nodes in the new order,
+        # then each node's surviving pods in NodeInfo.Pods order), replayed
+        self._log = [("node", st.nodes[n]) for n in names] + \
+                    [("pod", p, n) for n in names for p, _ in st.pods[n]]
+        self._replay()
 
     def Fork(self) -> None:  # noqa: N802
         self._apply(("fork",))

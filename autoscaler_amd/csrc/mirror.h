@@ -229,6 +229,8 @@ static_assert(SWEEP_MAP_INTS == CA_SWEEP_MAP_INTS, "casim.h map record size");
 // in), adv / succ (PROBE out), n_sensitive, map_ran / map_ok / map (MAP out)
 using SweepPhase = ca_sweep_phase;
 
+// ca_mirror_reorder_nodes' argument check (CA_OK, CA_EINVAL or CA_ESTATE; nothing changed)
+int mirror_reorder_check(const ca_mirror* m, const int32_t* order, int32_t n);
 int64_t removal_plan_sensitive_pods(const ca_removal_plan* p);
 bool removal_plan_phase_ok(const ca_removal_plan* p);             // no scope cut in the range
 int32_t sweep_fp_class(const int32_t* fp, int32_t n, int32_t L);  // class of L in a row's fit points
@@ -263,6 +265,15 @@ struct ca_mirror {
     enum { SS_FULL = 0, SS_STAGED, SS_ROWS_STAGED, SS_STATIC, SS_GROWTHS, SS_DEVICE_ROWS, SS_FILL_THREADS,
            SS_PLACED_THREADS, SS_N };
     int64_t sync_stat[SS_N] = {0};
+    // ca_mirror_reorder_nodes: the list order changed this many times since create (never
+    // reset: a removal plan remembers the epoch it was created in); counters of
+    // ca_mirror_reorder_stats (since create / Clear()); the pinned [order | inverse] pair and
+    // its device copy followed by the gathered columns (not a row buffer: no SS_GROWTHS)
+    int64_t order_epoch = 0;
+    enum { RS_CALLS = 0, RS_DEVICE, RS_LAST_US, RS_N };
+    int64_t reorder_stat[RS_N] = {0};
+    casim::HostBuf h_reorder;
+    casim::DevBuf d_reorder;
 
     // device pod table (mirror pods), appended lazily
     casim::DevPodTable d_pods;

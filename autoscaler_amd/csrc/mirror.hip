@@ -419,6 +419,61 @@ __global__ void k_remap_hints(int32_t* __restrict__ h, int32_t n, int32_t pos, i
     h[i] = v;
 }
 
+// ca_mirror_reorder_nodes: row k of the new order is row order[k] of the old one, for the
+// three columns at once in 16-byte chunks (NodeHot 2, NodeExt 5, NodeStatic 6 per row).
+// Thread t writes chunk t of the concatenation [hot | ext | static] of the scratch columns,
+// so a wave's stores are contiguous; its load is one of order[]'s rows.  order is a
+// permutation of 0..n-1 (checked on the host) and the scratch columns hold n rows.
+constexpr int32_t RO_HOT = (int32_t)(sizeof(NodeHot) / 16), RO_EXT = (int32_t)(sizeof(NodeExt) / 16),
+                  RO_STATIC = (int32_t)(sizeof(NodeStatic) / 16), RO_CHUNKS = RO_HOT + RO_EXT + RO_STATIC;
+static_assert(sizeof(NodeHot) % 16 == 0 && sizeof(NodeExt) % 16 == 0 && sizeof(NodeStatic) % 16 == 0, "16-byte chunks");
+static_assert(alignof(NodeHot) == 16 && alignof(NodeExt) == 16 && alignof(NodeStatic) == 16, "16-byte chunks");
+
+__global__ void __launch_bounds__(256) k_reorder_rows(const int32_t* __restrict__ order, int32_t n,
+                                                      const uint4* __restrict__ hot, const uint4* __restrict__ ext,
+                                                      const uint4* __restrict__ st, uint4* __restrict__ out_hot,
+                                                      uint4* __restrict__ out_ext, uint4* __restrict__ out_st) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t n_hot = (int64_t)n * RO_HOT, n_ext = (int64_t)n * RO_EXT, n_st = (int64_t)n * RO_STATIC;
+    if (t < n_hot) {
+        const int32_t k = (int32_t)(t / RO_HOT), c = (int32_t)(t % RO_HOT);
+        out_hot[t] = hot[(int64_t)order[k] * RO_HOT + c];
+    } else if (t < n_hot + n_ext) {
+        const int64_t u = t - n_hot;
+        const int32_t k = (int32_t)(u / RO_EXT), c = (int32_t)(u % RO_EXT);
+        out_ext[u] = ext[(int64_t)order[k] * RO_EXT + c];
+    } else if (t < n_hot + n_ext + n_st) {
+        const int64_t u = t - n_hot - n_ext;
+        const int32_t k = (int32_t)(u / RO_STATIC), c = (int32_t)(u % RO_STATIC);
+        out_st[u] = st[(int64_t)order[k] * RO_STATIC + c];
+    }
+}
+
+// ... and the resident hints follow their node: a hint to old position v becomes inv[v].
+// Codes < 0 (no hint, removed node) and values >= n (never a valid hint) are kept.
+__global__ void __launch_bounds__(256) k_reorder_hints(int32_t* __restrict__ h, int32_t n_hints,
+                                                       const int32_t* __restrict__ inv, int32_t n) {
+    const int32_t i = (int32_t)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i >= n_hints) return;
+    const int32_t v = h[i];
+    if (v >= 0 && v < n) h[i] = inv[v];
+}
+
+int mirror_reorder_check(const ca_mirror* m, const int32_t* order, int32_t n) {
+    if (!m || n < 0 || (size_t)n != m->nodes.size() || (n > 0 && !order)) return CA_EINVAL;
+    std::vector<uint64_t> seen(((size_t)n + 63) / 64, 0);                // one pass over a bitmap
+    for (int32_t k = 0; k < n; k++) {
+        const int32_t x = order[k];
+        if (x < 0 || x >= n) return CA_EINVAL;
+        uint64_t& w = seen[(size_t)x >> 6];
+        const uint64_t b = 1ull << (x & 63);
+        if (w & b) return CA_EINVAL;
+        w |= b;
+    }
+    if (m->depth > 0) return CA_ESTATE;                                  // the journal holds positions
+    return CA_OK;
+}
+
 }  // namespace casim
 
 using namespace casim;
@@ -1091,6 +1146,7 @@ int ca_mirror_clear(ca_mirror* m) {
     m->d_pods_synced = 0; m->d_terms_synced = 0;
     m->d_hints_n = 0;
     for (int64_t& c : m->sync_stat) c = 0;
+    for (int64_t& c : m->reorder_stat) c = 0;
     return CA_OK;
 }
 
@@ -1210,6 +1266,98 @@ int ca_mirror_sync_stats(const ca_mirror* m, int64_t* out, int32_t cap) {
     if (!m || (!out && cap > 0)) return CA_EINVAL;
     for (int32_t i = 0; i < cap && i < ca_mirror::SS_N; i++) out[i] = m->sync_stat[i];
     return ca_mirror::SS_N;
+}
+
+int ca_mirror_reorder_nodes(ca_mirror* m, const int32_t* order, int32_t n) {
+    int rc;
+    if ((rc = casim::mirror_reorder_check(m, order, n)) != CA_OK) return rc;
+    CA_HIP_CHECK(hipSetDevice(m->device));
+    const size_t N = (size_t)n, np = m->pods.size();
+    // rows resident and current apart from a few dirty ones: permuted on the device
+    const bool resident = N > 0 && m->d_rows == N && !m->all_dirty && !m->static_dirty;
+    const bool hints = N > 0 && m->d_hints_n > 0;
+    const size_t ob = (sizeof(int32_t) * N + 15) & ~(size_t)15;       // order | inverse, 16-byte aligned
+    int32_t* inv = nullptr;
+    std::vector<int32_t> inv_host;
+    if (resident || hints) {
+        // (an earlier reorder's copy out of the staging is done)
+        CA_HIP_CHECK(hipStreamSynchronize(m->stream));
+        if ((rc = m->h_reorder.reserve(2 * ob)) != CA_OK) return rc;
+        if ((rc = m->d_reorder.reserve(2 * ob + (resident ? (sizeof(NodeHot) + sizeof(NodeExt) + sizeof(NodeStatic)) * N : 0))) != CA_OK)
+            return rc;
+        std::memcpy(m->h_reorder.ptr, order, sizeof(int32_t) * N);
+        inv = reinterpret_cast<int32_t*>(m->h_reorder.as<char>() + ob);
+    } else {
+        inv_host.resize(N);
+        inv = inv_host.data();
+    }
+    for (int32_t k = 0; k < n; k++) inv[order[k]] = k;
+    // pending dirty rows go up by the usual path, at their old positions (nothing is dirty after)
+    if (resident && (rc = m->sync_nodes()) != CA_OK) return rc;
+    // host rows: moved (their pods vectors are not copied), then every pod's node
+    {
+        std::vector<casim::NodeRow> moved;
+        moved.reserve(std::max(m->nodes.capacity(), N));
+        for (int32_t k = 0; k < n; k++) moved.push_back(std::move(m->nodes[order[k]]));
+        m->nodes.swap(moved);
+    }
+    const int32_t T = np >= 65536 ? 8 : 1;
+    casim::parallel_run(T, [&](int32_t w) {
+        const size_t i0 = np * (size_t)w / (size_t)T, i1 = np * (size_t)(w + 1) / (size_t)T;
+        for (size_t i = i0; i < i1; i++) {
+            int32_t& x = m->pods[i].node;
+            if (x >= 0) x = inv[x];
+        }
+    });
+    if (!resident) {
+        // the next sync uploads every column in the new order
+        m->dirty_rows.clear();
+        m->dirty_flag.assign(N, 0);
+        m->all_dirty = true;
+        m->static_dirty = true;
+    }
+    m->order_epoch++;
+    m->reorder_stat[ca_mirror::RS_CALLS]++;
+    m->reorder_stat[ca_mirror::RS_LAST_US] = 0;
+    if (!resident && !hints) return CA_OK;
+    char* const d = m->d_reorder.as<char>();
+    const int32_t* d_order = reinterpret_cast<const int32_t*>(d);
+    const int32_t* d_inv = reinterpret_cast<const int32_t*>(d + ob);
+    CA_HIP_CHECK(hipEventRecord(m->ev0, m->stream));
+    CA_HIP_CHECK(hipMemcpyAsync(d, m->h_reorder.ptr, 2 * ob, hipMemcpyHostToDevice, m->stream));
+    if (resident) {
+        uint4* s_hot = reinterpret_cast<uint4*>(d + 2 * ob);
+        uint4* s_ext = s_hot + N * RO_HOT;
+        uint4* s_st = s_ext + N * RO_EXT;
+        const size_t chunks = N * (size_t)RO_CHUNKS;
+        hipLaunchKernelGGL(k_reorder_rows, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, m->stream, d_order, n,
+                           m->d_hot.as<const uint4>(), m->d_ext.as<const uint4>(), m->d_static.as<const uint4>(), s_hot,
+                           s_ext, s_st);
+        CA_HIP_CHECK(hipGetLastError());
+        // back into the row buffers: their addresses stay what the sweep's replayed graph and
+        // its device maps hold
+        CA_HIP_CHECK(hipMemcpyAsync(m->d_hot.ptr, s_hot, sizeof(NodeHot) * N, hipMemcpyDeviceToDevice, m->stream));
+        CA_HIP_CHECK(hipMemcpyAsync(m->d_ext.ptr, s_ext, sizeof(NodeExt) * N, hipMemcpyDeviceToDevice, m->stream));
+        CA_HIP_CHECK(hipMemcpyAsync(m->d_static.ptr, s_st, sizeof(NodeStatic) * N, hipMemcpyDeviceToDevice, m->stream));
+        m->reorder_stat[ca_mirror::RS_DEVICE]++;
+    }
+    if (hints) {
+        hipLaunchKernelGGL(k_reorder_hints, dim3((unsigned)((m->d_hints_n + 255) / 256)), dim3(256), 0, m->stream,
+                           m->d_pod_hints.as<int32_t>(), (int32_t)m->d_hints_n, d_inv, n);
+        CA_HIP_CHECK(hipGetLastError());
+    }
+    CA_HIP_CHECK(hipEventRecord(m->ev1, m->stream));
+    CA_HIP_CHECK(hipStreamSynchronize(m->stream));
+    float ms = 0;
+    CA_HIP_CHECK(hipEventElapsedTime(&ms, m->ev0, m->ev1));
+    m->reorder_stat[ca_mirror::RS_LAST_US] = (int64_t)(ms * 1000.0f + 0.5f);
+    return CA_OK;
+}
+
+int ca_mirror_reorder_stats(const ca_mirror* m, int64_t* out, int32_t cap) {
+    if (!m || (!out && cap > 0)) return CA_EINVAL;
+    for (int32_t i = 0; i < cap && i < ca_mirror::RS_N; i++) out[i] = m->reorder_stat[i];
+    return ca_mirror::RS_N;
 }
 
 int ca_mirror_fork(ca_mirror* m) {

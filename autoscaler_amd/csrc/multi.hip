@@ -108,6 +108,19 @@ int ca_multi_destroy(ca_multi* mm) {
     return CA_OK;
 }
 
+int ca_multi_reorder_nodes(ca_multi* mm, const int32_t* order, int32_t n) {
+    if (!mm) return CA_EINVAL;
+    for (ca_mirror* m : mm->m) {                    // all or none: every replica is checked first
+        const int rc = casim::mirror_reorder_check(m, order, n);
+        if (rc != CA_OK) return rc;
+    }
+    for (ca_mirror* m : mm->m) {
+        const int rc = ca_mirror_reorder_nodes(m, order, n);
+        if (rc != CA_OK) return rc;
+    }
+    return CA_OK;
+}
+
 // ---- Estimate -------------------------------------------------------------------------
 
 int ca_multi_estimate_plan_create(ca_multi* mm, const ca_pod_table* t, const int32_t* group_off,

@@ -2204,6 +2204,7 @@ struct ca_removal_plan {
     ca_mirror* m = nullptr;
     int32_t C = 0, M = 0, n = 0;
     int32_t C_all = 0;              // candidates of the call; C = the prefix before the scope cut
+    int64_t order_epoch = 0;        // the mirror's node order the candidates and the mask are positions in
     std::vector<int32_t> off_all;
     std::vector<int32_t> cand, status, off, moves;
     std::vector<uint8_t> mask;
@@ -2252,6 +2253,7 @@ int ca_removal_plan_create(ca_mirror* m, const int32_t* candidates, int32_t C, c
     C = casim::scope_cut(m, C, candidates, dest_mask, cand_status, move_off, move_pods);
     M = move_off[C] - move_off[0];
     p->m = m; p->C = C; p->M = M; p->n = n;
+    p->order_epoch = m->order_epoch;
     p->cand.assign(candidates, candidates + C);
     p->status = cand_status ? std::vector<int32_t>(cand_status, cand_status + C) : std::vector<int32_t>((size_t)C, 0);
     p->off.assign(move_off, move_off + C + 1);
@@ -2306,6 +2308,7 @@ int removal_plan_run_phase(ca_removal_plan* p, int32_t* hints, int32_t* last_ind
     if (!p || !last_index || (p->C_all > 0 && !results)) return CA_EINVAL;
     if (ph && ph->kind != SP_FULL && p->C < p->C_all) return CA_EINVAL;
     ca_mirror* m = p->m;
+    if (p->order_epoch != m->order_epoch) return CA_ESTATE;    // created before a ca_mirror_reorder_nodes
     CA_HIP_CHECK(hipSetDevice(m->device));
     m->sweep_stats.had_success = m->sweep_stats.lin_sensitive = 0;
     if (p->C_all == 0) return CA_OK;

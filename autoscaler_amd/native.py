@@ -124,6 +124,9 @@ def load() -> C.CDLL:
         "ca_mirror_set_hints": ([vp, vp, i32], C.c_int),
         "ca_mirror_get_hints": ([vp, vp, i32], C.c_int),
         "ca_mirror_sync_stats": ([vp, p(C.c_int64), i32], C.c_int),
+        "ca_mirror_reorder_nodes": ([vp, vp, i32], C.c_int),
+        "ca_mirror_reorder_stats": ([vp, p(C.c_int64), i32], C.c_int),
+        "ca_multi_reorder_nodes": ([vp, vp, i32], C.c_int),
         "ca_removal_candidate_ticks": ([vp, p(C.c_uint64), i32], C.c_int),
         "ca_removal_timings": ([vp, p(C.c_float), i32], C.c_int),
         "ca_filter_out_schedulable": ([vp, vp, vp, vp, i32, vp, i32, vp, p(i32), vp, vp, p(i32), p(C.c_uint64), p(i32)],
@@ -220,7 +223,7 @@ def exported_symbols() -> list[str]:
         "ca_removal_stats", "ca_removal_timings", "ca_removal_plan_create", "ca_removal_plan_run",
         "ca_removal_plan_destroy", "ca_removal_plan_sensitive_pods", "ca_removal_plan_phased",
         "ca_removal_plan_run_phase", "ca_sweep_compose", "ca_mirror_set_hints", "ca_mirror_get_hints",
-        "ca_mirror_sync_stats",
+        "ca_mirror_sync_stats", "ca_mirror_reorder_nodes", "ca_mirror_reorder_stats", "ca_multi_reorder_nodes",
         "ca_removal_candidate_ticks", "ca_filter_out_schedulable", "ca_try_schedule_pods", "ca_filter_stats",
         "ca_util_table_create", "ca_util_table_destroy", "ca_util_calculate", "ca_util_device_results",
         "ca_util_table_update", "ca_util_table_set_added", "ca_multi_create", "ca_multi_destroy",
@@ -682,6 +685,20 @@ class Mirror:
         names = ["full_syncs", "staged_syncs", "rows_staged", "static_uploads", "growths", "device_rows",
                  "fill_threads", "placed_threads"]
         return {nm: int(v) for nm, v in zip(names, out)}
+
+    def reorder_nodes(self, order) -> None:
+        """ca_mirror_reorder_nodes: the node now at position order[k] moves to position k (the
+        list the Go snapshot's next NodeInfos().List() returned); depth 0 only."""
+        o = np.ascontiguousarray(order, dtype=np.int32)
+        _check(self.lib.ca_mirror_reorder_nodes(self.h, ptr(o) if len(o) else None, len(o)),
+               "ca_mirror_reorder_nodes")
+
+    def reorder_stats(self) -> tuple:
+        """(reorders since create / clear, those permuted on the device, device time of the
+        last one in microseconds) (ca_mirror_reorder_stats)."""
+        out = (C.c_int64 * 3)()
+        self.lib.ca_mirror_reorder_stats(self.h, out, 3)
+        return tuple(int(v) for v in out)
 
     def candidate_ticks(self, n_candidates: int) -> np.ndarray:
         """Per candidate of the last sweep: device time of its simulation, us."""
@@ -1165,6 +1182,12 @@ class Multi:
     def for_each(self, fn):
         """Apply a snapshot change to every replica, in order."""
         return [fn(m) for m in self.mirrors]
+
+    def reorder_nodes(self, order) -> None:
+        """ca_multi_reorder_nodes: the same new node order on every replica, all or none."""
+        o = np.ascontiguousarray(order, dtype=np.int32)
+        _check(self.lib.ca_multi_reorder_nodes(self.h, ptr(o) if len(o) else None, len(o)),
+               "ca_multi_reorder_nodes")
 
     def close(self) -> None:
         if self.h:

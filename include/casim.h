@@ -597,6 +597,33 @@ int ca_mirror_get_hints(ca_mirror* m, int32_t* hints, int32_t n_pods);
  * threads of the last full-table fill, [7] host threads of the last placement batch
  * (FilterOutSchedulable / TrySchedulePods commits); returns 8. */
 int ca_mirror_sync_stats(const ca_mirror* m, int64_t* out, int32_t cap);
+/* Node order: the reference rebuilds its node list from a Go map whenever an
+ * unforked mutation cleared the cache, so a shim re-syncs the order at the start of each
+ * phase (filter-out, scale-up, scale-down).
+ * The node now at position order[k] moves to position k (k = 0..n-1): the list the next
+ * NodeInfos().List() of the Go snapshot returned.  n must equal the node count and order must
+ * be a permutation of 0..n-1 (else CA_EINVAL, nothing changed).  Only at fork depth 0
+ * (CA_ESTATE inside a fork: the journal holds positions).  Pod ids, every node's
+ * NodeInfo.Pods order and the scope-blocker count are unchanged; ca_mirror_pod_node reports
+ * new positions; resident hints (ca_mirror_set_hints) follow their node (hints.go keeps
+ * names); codes < 0 (none / removed node) are kept.  The caller's lastIndex is an integer
+ * into the list and is NOT remapped (the reference keeps the int across list rebuilds).
+ * Rows resident on the device are permuted there (a gather kernel; the row buffers keep
+ * their addresses); rows not resident are uploaded in the new order by the next call that
+ * reads them.
+ * Objects created before a reorder:
+ *   ca_removal_plan (also phased, and the blocks of a ca_multi_removal_plan) holds candidate
+ *     positions and a destination mask in the old order: every run entry point returns
+ *     CA_ESTATE; create a new plan.
+ *   ca_podset, ca_expansion_plan, ca_estimate_plan (and ca_multi_estimate_plan) hold pod
+ *     records, template rows and group lists only, nothing by node position: they stay valid
+ *     and give exactly the results of objects created after the reorder.
+ *   ca_util_table is the caller's own table by node index, not the mirror's: out of scope,
+ *     the caller rebuilds or re-indexes it. */
+int ca_mirror_reorder_nodes(ca_mirror* m, const int32_t* order, int32_t n);
+/* out[0] reorders since create/Clear, [1] of them permuted on the device (rows were
+ * resident), [2] device time of the last one in microseconds; returns 3. */
+int ca_mirror_reorder_stats(const ca_mirror* m, int64_t* out, int32_t cap);
 int ca_removal_timings(const ca_mirror* m, float* out, int32_t cap);
 int ca_removal_stats(const ca_mirror* m, int32_t* rounds, float* kernel_ms, float* total_ms);
 /* Diagnostics: device wall-clock ticks (100 MHz) each candidate's simulation took in the
@@ -759,6 +786,9 @@ int ca_util_device_results(const ca_util_table* t, const ca_util_info** out);
 typedef struct ca_multi ca_multi;
 int ca_multi_create(ca_mirror* const* mirrors, int32_t n, ca_multi** out);
 int ca_multi_destroy(ca_multi* mm);   /* the mirrors stay the caller's */
+/* ca_mirror_reorder_nodes on every mirror; all or none: each is checked before any changes
+ * (a bad permutation, a wrong n or a fork on one replica leaves all of them as they were). */
+int ca_multi_reorder_nodes(ca_multi* mm, const int32_t* order, int32_t n);   /* every mirror; all or none */
 
 /* Estimate batch (ca_estimate_batch semantics, prefix protocol included) over the mirrors'
  * blocks of node groups.  sched_pod is required (host memory; page-locked memory from
