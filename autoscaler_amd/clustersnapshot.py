@@ -13,6 +13,7 @@ log is replayed into the backend, so one encoding always covers the whole mirror
 from __future__ import annotations
 
 import copy
+import weakref
 from dataclasses import dataclass, field
 from typing import Optional
 
@@ -33,6 +34,14 @@ class NodeInfo:
 
     def Node(self) -> Node:  # noqa: N802 - reference spelling
         return self.node
+
+
+# sync_replica's stamps: replica backend -> (token of the snapshot it was loaded from, that
+# snapshot's version then).  Shared by all snapshots, so a replica reloaded by another snapshot
+# in between is seen as stale; weak keys, so nothing is written on the backend object and a
+# closed replica drops out; the token object is held by the stamp, so it cannot be taken for a
+# later snapshot's (an id() could be reused).
+_REPLICA_STAMPS: "weakref.WeakKeyDictionary" = weakref.WeakKeyDictionary()
 
 
 class _State:
@@ -83,6 +92,9 @@ class ClusterSnapshot:
         self._log: list = []
         self._state = _State()
         self._stack: list[_State] = []
+        self._token = object()            # this snapshot, in the replicas' stamps
+        self._version = 0                 # bumped by everything that changes the log or its encoding
+        self.replica_loads = 0            # sync_replica calls that reloaded their mirror
 
     # -- encoding / replay ------------------------------------------------------
     def _sizes(self):
@@ -102,38 +114,68 @@ class ClusterSnapshot:
         self._log = []
         self._state = _State()
         self._stack = []
+        self._version += 1
         self.backend.clear()
         for op in log:
             self._apply(op)
 
     def _apply(self, op) -> None:
+        self._apply_to(self.backend, self._state, self._stack, op)
+        self._log.append(op)
+        self._version += 1
+
+    def _apply_to(self, backend, st: _State, stack, op) -> None:
+        """One log op on `backend`, whose bookkeeping is `st` (`stack`: the fork stack, or None
+        for a replica, which never reverts on its own)."""
         kind = op[0]
-        st = self._state
         if kind == "node":
             rec = self.interner.encode_nodes([op[1]])
             st.add_node(op[1])
-            self.backend.add_nodes(rec)
+            backend.add_nodes(rec)
         elif kind == "pod":
             pod, node = op[1], op[2]
             if node not in st.pos:
                 raise NodeNotFoundError(node)
             table = self.interner.encode_pods([pod])
-            ids = self.backend.add_pods(table, [0], [st.pos[node]])
+            ids = backend.add_pods(table, [0], [st.pos[node]])
             st.add_pod(pod, node, int(ids[0]))
         elif kind == "rmpod":
             pid = st.remove_pod(op[1], op[2], op[3])
-            self.backend.remove_pod(pid)
+            backend.remove_pod(pid)
         elif kind == "rmnode":
             pos = st.pos[op[1]]
-            self.backend.remove_node(pos)
+            backend.remove_node(pos)
             st.remove_node(op[1])
         elif kind == "order":
-            self.backend.reorder_nodes([st.pos[n] for n in op[1]])
+            backend.reorder_nodes([st.pos[n] for n in op[1]])
             st.set_order(op[1])
         elif kind == "fork":
-            self._stack.append(copy.deepcopy(st))
-            self.backend.fork()
-        self._log.append(op)
+            if stack is not None:
+                stack.append(copy.deepcopy(st))
+            backend.fork()
+
+    def sync_replica(self, mirror) -> bool:
+        """Make `mirror` (another backend object: a replica of native.Multi) hold this snapshot:
+        clear it and apply the log to it with the current interner, as _replay does to the
+        backend.  The mirror is stamped (in a table of this module, not on the object) with the
+        snapshot and version it was loaded from, and a call that finds the stamp current reloads
+        nothing and returns False: the version changes with every op applied or recorded, every
+        replay, Revert, Commit and Clear.  The replica must be changed through this call only."""
+        if mirror is self.backend:
+            return False
+        stamp = (self._token, self._version)
+        if _REPLICA_STAMPS.get(mirror) == stamp:
+            return False
+        _REPLICA_STAMPS.pop(mirror, None)
+        mirror.clear()
+        st = _State()
+        for op in self._log:
+            if op[0] == "order" and not hasattr(mirror, "reorder_nodes"):
+                raise TypeError("sync_replica: the log holds a SetNodeOrder the replica cannot apply")
+            self._apply_to(mirror, st, None, op)
+        _REPLICA_STAMPS[mirror] = stamp
+        self.replica_loads += 1
+        return True
 
     # -- ClusterSnapshot interface ------------------------------------------------
     def AddNode(self, node: Node) -> None:  # noqa: N802
@@ -198,6 +240,7 @@ class ClusterSnapshot:
         self._state = self._stack.pop()
         i = max(i for i, op in enumerate(self._log) if op[0] == "fork")
         del self._log[i:]
+        self._version += 1
 
     def Commit(self) -> None:  # noqa: N802
         if not self._stack:
@@ -206,6 +249,7 @@ class ClusterSnapshot:
         self._stack.pop()
         i = max(i for i, op in enumerate(self._log) if op[0] == "fork")
         del self._log[i]
+        self._version += 1
 
     def Clear(self) -> None:  # noqa: N802
         self.backend.clear()
@@ -213,6 +257,7 @@ class ClusterSnapshot:
         self._state = _State()
         self._stack = []
         self.interner = Interner()
+        self._version += 1
 
     def record_added_pods(self, placed: list) -> None:
         """Pods the backend already added (a batched AddPod, e.g. FilterOutSchedulable):
@@ -221,6 +266,7 @@ class ClusterSnapshot:
         for pod, node, pid in placed:
             st.add_pod(pod, node, int(pid))
             self._log.append(("pod", pod, node))
+        self._version += 1
 
     def record_moves(self, groups: list) -> None:
         """Moves the backend already committed (the planner, ca_plan_removals), recorded as
@@ -235,6 +281,7 @@ class ClusterSnapshot:
             for _, cp, dest, pid in moves:
                 st.add_pod(cp, dest, int(pid))
                 self._log.append(("pod", cp, dest))
+        self._version += 1
 
     # -- NodeInfos() lister ----------------------------------------------------
     def List(self) -> list:  # noqa: N802

@@ -372,6 +372,7 @@ struct OptionSumsScratch {
 struct MissingPodsScratch {
     DevBuf d_in, d_out;             // [off | n_scheduled | tile prefix] of the rows; [n_missing | bad ids | first]
     DevBuf d_rows;                  // one batch of bitmap rows over the pod set
+    DevBuf d_req;                   // a required list uploaded from another device's plan (multi.hip)
     HostBuf h;                      // page-locked staging of d_in and d_out
     std::vector<int32_t> row_of, row_group;   // group -> row or -1; row -> group
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -410,4 +411,24 @@ struct PlanLists {
     PriceSumsScratch* price = nullptr;
 };
 void estimate_plan_lists(const ca_estimate_plan* p, PlanLists* out);
+
+// The required list of filterNodeGroupsByPods as k_test_required reads it: ids [off, off + n)
+// of a device buffer of `total` ids on the plan's device.  A plan's own group g is
+// (d_sched_pod, total, h_off[g], h_nsched[g]); a list exported from another device and
+// uploaded is (buf, n, 0, n).  first_missing positions are relative to `off` either way.
+struct RequiredList {
+    const int32_t* d_ids = nullptr;
+    int32_t total = 0, off = 0, n = 0;
+};
+// The body of ca_estimate_plan_groups_missing_pods (nodegroupset.hip).  ext == nullptr: the
+// required list is the plan's own group `required_group`.  Otherwise `*ext` is the required
+// list, required_group is ignored and no candidate is "the required group itself".
+int estimate_plan_missing_pods(ca_estimate_plan* p, const RequiredList* ext, int32_t required_group,
+                               const int32_t* groups, int32_t n_groups, int32_t* n_missing, int32_t* first_missing);
+// The sharded plan's exchange (multi.hip): the first n ids of `group`'s list into page-locked
+// h_ids, one stream-ordered D2H; and the core above with n ids of page-locked h_ids uploaded
+// into the plan's own scratch as the required list.
+int estimate_plan_export_list(const ca_estimate_plan* p, int32_t group, int32_t* h_ids, int32_t n);
+int estimate_plan_missing_pods_of(ca_estimate_plan* p, const int32_t* h_ids, int32_t n, const int32_t* groups,
+                                  int32_t n_groups, int32_t* n_missing, int32_t* first_missing);
 }  // namespace casim

@@ -9,7 +9,11 @@
 // here: walking the blocks in order, a block that ran from a wrong lastIndex is re-run
 // from the exact one when its output depends on it (a FitsAnyNode success whose scan
 // started at the input), and otherwise only has its lastIndex fields re-based.  No data
-// crosses devices: every block writes its own slice of the caller's result arrays.
+// crosses devices in a run: every block writes its own slice of the caller's result arrays.
+// After a resident Estimate run the one-device readers of ScaleUp (option sums, price sums,
+// one group's list, filterNodeGroupsByPods) work over the blocks; the last of them is the
+// only call that moves list data from one device to another (through host memory).
+#include <algorithm>
 #include <thread>
 #include <chrono>
 
@@ -69,6 +73,23 @@ struct ca_multi_estimate_plan {
     std::vector<ca_estimate_plan*> pl;
     int32_t reruns = 0;
     int32_t rerun_units = 0;                  // groups in the re-run blocks of the last run
+    // ScaleUp after the run (DESIGN.md §6 "ScaleUp on sharded plans"): the readers work only after
+    // a resident run (sched_pod == NULL) that returned CA_OK, and on this plan's results of that
+    // run, not the inner plans' (a block behind a prefix cut ran on its device all the same)
+    bool resident = false;
+    std::vector<ca_estimate_result> last;     // results[] of the last run
+    std::vector<int32_t> nsched;              // n_scheduled of last[], 0 for a group that is not CA_OK
+    casim::HostBuf h_req;                     // the required list on its way to the other blocks
+    std::vector<float> reader_ms[3];          // per block: kernel ms of the last call of each reader
+    int64_t exported_bytes = 0;               // last groups_missing_pods: bytes of the exported list,
+    int32_t importing_blocks = 0;             // and the blocks that uploaded it
+    int32_t block_of(int32_t g) const {
+        return (int32_t)(std::upper_bound(gb.begin(), gb.end(), g) - gb.begin()) - 1;
+    }
+    bool block_live(int32_t d) const {        // some group of the block is CA_OK
+        for (int32_t g = gb[d]; g < gb[d + 1]; g++) if (last[g].status == CA_OK) return true;
+        return false;
+    }
     ~ca_multi_estimate_plan() {
         for (auto* p : pl) if (p) ca_estimate_plan_destroy(p);
         for (auto* s : ps) if (s) ca_podset_destroy(s);
@@ -155,14 +176,30 @@ int ca_multi_estimate_plan_create(ca_multi* mm, const ca_pod_table* t, const int
 
 int ca_multi_estimate_plan_run(ca_multi_estimate_plan* p, const ca_limiter* limiter, int32_t* last_index,
                                ca_estimate_result* results, int32_t* sched_pod, int32_t* sched_node) {
-    if (!p || !limiter || !last_index || (p->G > 0 && (!results || !sched_pod))) return CA_EINVAL;
+    if (!p) return CA_EINVAL;
+    p->resident = false;                                    // until this call returns CA_OK as a resident run
+    if (!limiter || !last_index || (p->G > 0 && !results)) return CA_EINVAL;
+    // sched_pod == NULL: a resident run, every block's lists stay in its plan (casim.h)
+    if (!sched_pod && sched_node) return CA_EINVAL;
+    // A resident run without groups: nothing to run, the readers answer CA_OK.  Only the resident
+    // form is cut short here.  A host-list run without groups stays on the path below, which it
+    // always took and whose answers must not change: the empty block's plan is called and, as
+    // before, rejects a NULL results (a resident caller with G == 0 has no results array to pass).
+    if (p->G == 0 && !sched_pod) {
+        p->last.clear();
+        p->nsched.clear();
+        p->reruns = p->rerun_units = 0;
+        p->resident = true;
+        return CA_OK;
+    }
     const int32_t D = (int32_t)p->gb.size() - 1;
     const int32_t L0 = *last_index;
     std::vector<int32_t> lin((size_t)D, L0), lout((size_t)D, L0), sens((size_t)D, 0), succ((size_t)D, 0);
     auto run = [&](int32_t d, int32_t from) {
         const int32_t g0 = p->gb[d];
         int32_t li = from;
-        int r = ca_estimate_plan_run(p->pl[d], limiter, &li, results + g0, sched_pod + p->off[g0],
+        int r = ca_estimate_plan_run(p->pl[d], limiter, &li, results + g0,
+                                     sched_pod ? sched_pod + p->off[g0] : nullptr,
                                      sched_node ? sched_node + p->off[g0] : nullptr);
         if (r != CA_OK) return r;
         lin[d] = from;
@@ -187,7 +224,7 @@ int ca_multi_estimate_plan_run(ca_multi_estimate_plan* p, const ca_limiter* limi
                 r.status = CA_ENOTRUN;
                 r.evals = 0;
             }
-            std::fill(sched_pod + p->off[g0], sched_pod + p->off[g1], -1);
+            if (sched_pod) std::fill(sched_pod + p->off[g0], sched_pod + p->off[g1], -1);
             if (sched_node) std::fill(sched_node + p->off[g0], sched_node + p->off[g1], -1);
             continue;
         }
@@ -205,6 +242,183 @@ int ca_multi_estimate_plan_run(ca_multi_estimate_plan* p, const ca_limiter* limi
         for (int32_t g = g0; g < g1; g++) if (results[g].status == CA_EUNSUPPORTED) cut = true;
     }
     *last_index = cur;
+    p->last.assign(results, results + p->G);
+    p->nsched.resize((size_t)p->G);
+    for (int32_t g = 0; g < p->G; g++) p->nsched[g] = results[g].status == CA_OK ? results[g].n_scheduled : 0;
+    p->resident = sched_pod == nullptr;
+    return CA_OK;
+}
+
+// ---- ScaleUp after a resident run: the one-device readers over the blocks ----
+// Every reader runs its blocks concurrently into the block's slice of the caller's arrays, then
+// the plan's own results of the run decide: a group that is not CA_OK here reads as an empty
+// list whatever its block's plan holds.  A block without a CA_OK group launches nothing.
+
+int ca_multi_estimate_plan_option_sums(ca_multi_estimate_plan* p, int64_t* req_milli_cpu, int64_t* req_memory) {
+    if (!p || (p->G > 0 && (!req_milli_cpu || !req_memory))) return CA_EINVAL;
+    if (!p->resident) return CA_ESTATE;
+    const int32_t D = (int32_t)p->gb.size() - 1;
+    std::vector<float>& ms = p->reader_ms[CA_MULTI_READER_SUMS];
+    ms.assign((size_t)D, 0.0f);
+    if (p->G == 0) return CA_OK;
+    return for_blocks(D, [&](int32_t d) {
+        const int32_t g0 = p->gb[d], g1 = p->gb[d + 1];
+        if (p->block_live(d)) {
+            int r = ca_estimate_plan_option_sums(p->pl[d], req_milli_cpu + g0, req_memory + g0);
+            if (r != CA_OK) return r;
+            if ((r = ca_estimate_plan_option_sums_ms(p->pl[d], &ms[d])) != CA_OK) return r;
+        }
+        for (int32_t g = g0; g < g1; g++)
+            if (p->last[g].status != CA_OK) req_milli_cpu[g] = req_memory[g] = 0;
+        return (int)CA_OK;
+    });
+}
+
+int ca_multi_estimate_plan_option_price_sums(ca_multi_estimate_plan* p, const double* pod_price, int32_t n_prices,
+                                             double* total_pod_price) {
+    if (!p || n_prices < 0 || (n_prices > 0 && !pod_price) || (p->G > 0 && !total_pod_price)) return CA_EINVAL;
+    const int32_t D = (int32_t)p->gb.size() - 1;
+    for (int32_t d = 0; d < D; d++)                          // every block's pod set is the one pod table
+        if (p->ps[d] && n_prices != p->ps[d]->n_host) return CA_EINVAL;
+    if (!p->resident) return CA_ESTATE;
+    std::vector<float>& ms = p->reader_ms[CA_MULTI_READER_PRICE];
+    ms.assign((size_t)D, 0.0f);
+    if (p->G == 0) return CA_OK;
+    return for_blocks(D, [&](int32_t d) {
+        const int32_t g0 = p->gb[d], g1 = p->gb[d + 1];
+        if (p->block_live(d)) {
+            int r = ca_estimate_plan_option_price_sums(p->pl[d], pod_price, n_prices, total_pod_price + g0);
+            if (r != CA_OK) return r;
+            if ((r = ca_estimate_plan_option_price_sums_ms(p->pl[d], &ms[d])) != CA_OK) return r;
+        }
+        for (int32_t g = g0; g < g1; g++)
+            if (p->last[g].status != CA_OK) total_pod_price[g] = 0.0;
+        return (int)CA_OK;
+    });
+}
+
+int ca_multi_estimate_plan_fetch_group(const ca_multi_estimate_plan* p, int32_t group, int32_t* sched_pod,
+                                       int32_t cap, int32_t* n) {
+    if (!p || !n || cap < 0 || (cap > 0 && !sched_pod)) return CA_EINVAL;
+    if (group < 0 || group >= p->G) return CA_EINVAL;
+    if (!p->resident) return CA_ESTATE;
+    const int32_t ns = p->nsched[group];
+    *n = ns;
+    if (ns > cap) return CA_ECAPACITY;
+    if (ns == 0) return CA_OK;
+    const int32_t d = p->block_of(group);
+    int32_t got = 0;
+    const int rc = ca_estimate_plan_fetch_group(p->pl[d], group - p->gb[d], sched_pod, cap, &got);
+    if (rc != CA_OK) return rc;
+    if (got != ns) { set_last_error("sharded fetch: a block's list length differs from the run's results"); return CA_EDEVICE; }
+    return CA_OK;
+}
+
+int ca_multi_estimate_plan_fetch(const ca_multi_estimate_plan* p, int32_t* sched_pod) {
+    if (!p || (p->G > 0 && p->off[p->G] > 0 && !sched_pod)) return CA_EINVAL;
+    if (!p->resident) return CA_ESTATE;
+    if (p->G == 0) return CA_OK;
+    const int32_t D = (int32_t)p->gb.size() - 1;
+    return for_blocks(D, [&](int32_t d) {
+        const int32_t g0 = p->gb[d], g1 = p->gb[d + 1];
+        if (p->block_live(d) && p->off[g1] > p->off[g0]) {
+            const int r = ca_estimate_plan_fetch(p->pl[d], sched_pod + p->off[g0]);
+            if (r != CA_OK) return r;
+        }
+        for (int32_t g = g0; g < g1; g++)                    // behind n_scheduled: stale ids of the block's plan
+            std::fill(sched_pod + p->off[g] + p->nsched[g], sched_pod + p->off[g + 1], -1);
+        return (int)CA_OK;
+    });
+}
+
+int ca_multi_estimate_plan_groups_missing_pods(ca_multi_estimate_plan* p, int32_t required_group,
+                                               const int32_t* groups, int32_t n_groups, int32_t* n_missing,
+                                               int32_t* first_missing) {
+    if (!p || n_groups < 0 || (n_groups > 0 && (!groups || !n_missing))) return CA_EINVAL;
+    if (required_group < 0 || required_group >= p->G) return CA_EINVAL;
+    for (int32_t k = 0; k < n_groups; k++) if (groups[k] < 0 || groups[k] >= p->G) return CA_EINVAL;
+    if (!p->resident) return CA_ESTATE;
+    const int32_t D = (int32_t)p->gb.size() - 1;
+    std::vector<float>& ms = p->reader_ms[CA_MULTI_READER_MISSING];
+    ms.assign((size_t)D, 0.0f);
+    p->exported_bytes = 0;
+    p->importing_blocks = 0;
+    if (n_groups == 0) return CA_OK;
+    // Slots the run's lengths answer, by this plan's results (ca_estimate_plan_groups_missing_pods
+    // has the rules); every other slot is a bitmap row in the block that holds its group.  Such a
+    // group is CA_OK with pods, so its block is not behind a cut and its plan's list is the run's.
+    const int32_t req_n = p->nsched[required_group];
+    struct Part { std::vector<int32_t> slot, group, nm, first; };
+    std::vector<Part> part((size_t)D);
+    for (int32_t k = 0; k < n_groups; k++) {
+        const int32_t g = groups[k];
+        if (req_n == 0 || g == required_group) {
+            n_missing[k] = 0;
+            if (first_missing) first_missing[k] = -1;
+        } else if (p->nsched[g] == 0) {
+            n_missing[k] = req_n;
+            if (first_missing) first_missing[k] = 0;
+        } else {
+            const int32_t d = p->block_of(g);
+            part[d].slot.push_back(k);
+            part[d].group.push_back(g - p->gb[d]);
+        }
+    }
+    const int32_t owner = p->block_of(required_group);
+    std::vector<int32_t> todo;
+    for (int32_t d = 0; d < D; d++) {
+        if (part[d].slot.empty()) continue;
+        todo.push_back(d);
+        part[d].nm.assign(part[d].slot.size(), 0);
+        part[d].first.assign(part[d].slot.size(), -1);
+        if (d != owner) p->importing_blocks++;
+    }
+    if (todo.empty()) return CA_OK;
+    int rc;
+    // The one place data crosses devices: a candidate row outside the owner's block needs the
+    // required list on its own device.  The owner exports the counted ids once, through
+    // page-locked memory of this plan; no peer copy (the mirrors may even share a device).
+    if (p->importing_blocks > 0) {
+        if ((rc = p->h_req.reserve(sizeof(int32_t) * (size_t)req_n)) != CA_OK) return rc;
+        if ((rc = casim::estimate_plan_export_list(p->pl[owner], required_group - p->gb[owner],
+                                                   p->h_req.as<int32_t>(), req_n)) != CA_OK)
+            return rc;
+        p->exported_bytes = (int64_t)sizeof(int32_t) * req_n;
+    }
+    rc = for_blocks((int32_t)todo.size(), [&](int32_t i) {
+        const int32_t d = todo[i];
+        Part& q = part[d];
+        const int32_t nq = (int32_t)q.slot.size();
+        int32_t* first = first_missing ? q.first.data() : nullptr;
+        int r = d == owner
+                    ? ca_estimate_plan_groups_missing_pods(p->pl[d], required_group - p->gb[d], q.group.data(), nq,
+                                                           q.nm.data(), first)
+                    : casim::estimate_plan_missing_pods_of(p->pl[d], p->h_req.as<int32_t>(), req_n, q.group.data(),
+                                                           nq, q.nm.data(), first);
+        if (r != CA_OK) return r;
+        return ca_estimate_plan_groups_missing_pods_ms(p->pl[d], &ms[d]);
+    });
+    if (rc != CA_OK) return rc;
+    for (int32_t d : todo)
+        for (size_t i = 0; i < part[d].slot.size(); i++) {
+            n_missing[part[d].slot[i]] = part[d].nm[i];
+            if (first_missing) first_missing[part[d].slot[i]] = part[d].first[i];
+        }
+    return CA_OK;
+}
+
+int ca_multi_estimate_plan_reader_ms(const ca_multi_estimate_plan* p, int32_t which, float* ms, int32_t cap) {
+    if (!p || which < 0 || which > CA_MULTI_READER_MISSING || cap < 0 || (cap > 0 && !ms)) return CA_EINVAL;
+    const int32_t D = (int32_t)p->gb.size() - 1;
+    const std::vector<float>& v = p->reader_ms[which];
+    for (int32_t d = 0; d < D && d < cap; d++) ms[d] = d < (int32_t)v.size() ? v[d] : 0.0f;
+    return D;
+}
+
+int ca_multi_estimate_plan_export_stats(const ca_multi_estimate_plan* p, int64_t* bytes, int32_t* blocks) {
+    if (!p) return CA_EINVAL;
+    if (bytes) *bytes = p->exported_bytes;
+    if (blocks) *blocks = p->importing_blocks;
     return CA_OK;
 }
 
@@ -235,6 +449,7 @@ int ca_multi_estimate_batch(ca_multi* mm, const ca_pod_table* t, const int32_t* 
                             const ca_template* templates, int32_t n_groups, const ca_limiter* limiter,
                             int32_t* last_index, ca_estimate_result* results, int32_t* sched_pod,
                             int32_t* sched_node) {
+    if (n_groups > 0 && !sched_pod) return CA_EINVAL;       // (a resident run of a plan destroyed below)
     ca_multi_estimate_plan* p = nullptr;
     int rc = ca_multi_estimate_plan_create(mm, t, group_off, pod_idx, templates, n_groups, &p);
     if (rc != CA_OK) return rc;

@@ -10,6 +10,11 @@
 // The reference builds one map[*Pod]bool per candidate; here a candidate is one bitmap row over
 // the pod set (k_mark_lists) and the required list is tested against every row
 // (k_test_required).  Pods are compared by pod-set index.
+//
+// The body is casim::estimate_plan_missing_pods, which takes the required list as a
+// (device pointer, total, offset, n) source: the plan's own group for the entry point above, a
+// list exported by another device's plan and uploaded here for the sharded plan (multi.hip:
+// estimate_plan_export_list / estimate_plan_missing_pods_of).
 #include "mirror.h"
 
 #include <algorithm>
@@ -172,17 +177,21 @@ __global__ void __launch_bounds__(MP_THREADS) k_test_required(const int32_t* __r
 }  // namespace
 }  // namespace casim
 
-using namespace casim;
+namespace casim {
 
-extern "C" {
-
-int ca_estimate_plan_groups_missing_pods(ca_estimate_plan* p, int32_t required_group, const int32_t* groups,
-                                         int32_t n_groups, int32_t* n_missing, int32_t* first_missing) {
+int estimate_plan_missing_pods(ca_estimate_plan* p, const RequiredList* ext, int32_t required_group,
+                               const int32_t* groups, int32_t n_groups, int32_t* n_missing, int32_t* first_missing) {
     if (!p || n_groups < 0 || (n_groups > 0 && (!groups || !n_missing))) return CA_EINVAL;
     PlanLists v;
     estimate_plan_lists(p, &v);
     const int32_t G = v.G;
-    if (required_group < 0 || required_group >= G) return CA_EINVAL;
+    if (ext) {
+        if (ext->n < 0 || ext->off < 0 || (int64_t)ext->off + ext->n > ext->total || (ext->n > 0 && !ext->d_ids))
+            return CA_EINVAL;
+        required_group = -1;                               // no candidate is the required group itself
+    } else if (required_group < 0 || required_group >= G) {
+        return CA_EINVAL;
+    }
     for (int32_t k = 0; k < n_groups; k++) if (groups[k] < 0 || groups[k] >= G) return CA_EINVAL;
     if (!v.final_lists) return CA_ESTATE;
     MissingPodsScratch& sc = *v.missing;
@@ -192,7 +201,11 @@ int ca_estimate_plan_groups_missing_pods(ca_estimate_plan* p, int32_t required_g
         const int32_t n = v.h_nsched[g];
         if (n < 0 || n > v.h_off[g + 1] - v.h_off[g]) { set_last_error("missing pods: n_scheduled outside its group"); return CA_EDEVICE; }
     }
-    const int32_t req_a = v.h_off[required_group], req_n = v.h_nsched[required_group];
+    // the required list: the plan's own group, or the caller's source
+    const int32_t* const req_ids = ext ? ext->d_ids : v.d_sched_pod;
+    const int32_t req_total = ext ? ext->total : v.total;
+    const int32_t req_a = ext ? ext->off : v.h_off[required_group];
+    const int32_t req_n = ext ? ext->n : v.h_nsched[required_group];
     // Slots the lists' lengths answer: an empty required list is included in anything, a group
     // includes itself, an empty candidate misses every position.  No other inclusion follows
     // from the lengths (either list may repeat an id), so every other distinct candidate is a row.
@@ -226,6 +239,9 @@ int ca_estimate_plan_groups_missing_pods(ca_estimate_plan* p, int32_t required_g
     // d_in: [row offset | row n_scheduled | tile prefix (R + 1)]; d_out: [n_missing R | bad 1 | first R]
     const size_t n_in = 3 * (size_t)R + 1, n_out = 2 * (size_t)R + 1;
     const size_t out_at = (n_in * sizeof(int32_t) + 15) & ~(size_t)15;
+    // the plan's device before any reserve: DevBuf allocates on the calling thread's current
+    // device, and the sharded plan calls this on threads that have not chosen one (multi.hip)
+    CA_HIP_CHECK(hipSetDevice(v.m->device));
     int rc;
     if ((rc = sc.h.reserve(out_at + n_out * sizeof(int32_t))) != CA_OK) return rc;
     if ((rc = sc.d_in.reserve(n_in * sizeof(int32_t))) != CA_OK) return rc;
@@ -247,7 +263,6 @@ int ca_estimate_plan_groups_missing_pods(ca_estimate_plan* p, int32_t required_g
     const int64_t req_tiles = ((int64_t)(req_a + req_n) - (req_a & ~3) + MP_TILE - 1) / MP_TILE;
     int32_t* h_out = reinterpret_cast<int32_t*>(static_cast<char*>(sc.h.ptr) + out_at);
 
-    CA_HIP_CHECK(hipSetDevice(v.m->device));
     hipStream_t st = v.m->stream;
     if (!sc.ev0) {
         CA_HIP_CHECK(hipEventCreate(&sc.ev0));
@@ -277,7 +292,7 @@ int ca_estimate_plan_groups_missing_pods(ca_estimate_plan* p, int32_t required_g
                            n_pods, d_bad);
         CA_HIP_CHECK(hipGetLastError());
         hipLaunchKernelGGL(k_test_required, dim3((uint32_t)req_tiles, (uint32_t)chunks), dim3(MP_THREADS), 0, st,
-                           v.d_sched_pod, v.total, req_a, req_n, sc.d_rows.as<uint32_t>(), W, nb, (int32_t)rows_blk,
+                           req_ids, req_total, req_a, req_n, sc.d_rows.as<uint32_t>(), W, nb, (int32_t)rows_blk,
                            n_pods, d_nmiss + r0, d_first + r0, d_bad);
         CA_HIP_CHECK(hipGetLastError());
     }
@@ -297,6 +312,55 @@ int ca_estimate_plan_groups_missing_pods(ca_estimate_plan* p, int32_t required_g
         if (first_missing) first_missing[k] = h_out[R + 1 + r] == INT32_MAX ? -1 : h_out[R + 1 + r];
     }
     return CA_OK;
+}
+
+int estimate_plan_export_list(const ca_estimate_plan* p, int32_t group, int32_t* h_ids, int32_t n) {
+    if (!p) return CA_EINVAL;
+    PlanLists v;
+    estimate_plan_lists(p, &v);
+    if (group < 0 || group >= v.G || n < 0 || (n > 0 && !h_ids)) return CA_EINVAL;
+    if (!v.final_lists) return CA_ESTATE;
+    if (n > v.h_nsched[group] || n > v.h_off[group + 1] - v.h_off[group]) return CA_EINVAL;
+    if (n == 0) return CA_OK;
+    CA_HIP_CHECK(hipSetDevice(v.m->device));
+    CA_HIP_CHECK(hipMemcpyAsync(h_ids, v.d_sched_pod + v.h_off[group], sizeof(int32_t) * (size_t)n,
+                                hipMemcpyDeviceToHost, v.m->stream));
+    CA_HIP_CHECK(hipStreamSynchronize(v.m->stream));
+    return CA_OK;
+}
+
+int estimate_plan_missing_pods_of(ca_estimate_plan* p, const int32_t* h_ids, int32_t n, const int32_t* groups,
+                                  int32_t n_groups, int32_t* n_missing, int32_t* first_missing) {
+    if (!p || n < 0 || (n > 0 && !h_ids)) return CA_EINVAL;
+    PlanLists v;
+    estimate_plan_lists(p, &v);
+    MissingPodsScratch& sc = *v.missing;
+    RequiredList req;
+    if (n > 0) {
+        // the upload is ordered before the core's kernels by the plan's stream
+        CA_HIP_CHECK(hipSetDevice(v.m->device));
+        int rc;
+        if ((rc = sc.d_req.reserve(sizeof(int32_t) * (size_t)n)) != CA_OK) return rc;
+        CA_HIP_CHECK(hipMemcpyAsync(sc.d_req.ptr, h_ids, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice,
+                                    v.m->stream));
+        req.d_ids = sc.d_req.as<int32_t>();
+    }
+    req.total = req.n = n;
+    const int rc = estimate_plan_missing_pods(p, &req, -1, groups, n_groups, n_missing, first_missing);
+    // (a core that returned without a launch has not waited for the upload: h_ids is the caller's again)
+    if (n > 0) CA_HIP_CHECK(hipStreamSynchronize(v.m->stream));
+    return rc;
+}
+
+}  // namespace casim
+
+using namespace casim;
+
+extern "C" {
+
+int ca_estimate_plan_groups_missing_pods(ca_estimate_plan* p, int32_t required_group, const int32_t* groups,
+                                         int32_t n_groups, int32_t* n_missing, int32_t* first_missing) {
+    return estimate_plan_missing_pods(p, nullptr, required_group, groups, n_groups, n_missing, first_missing);
 }
 
 int ca_estimate_plan_groups_missing_pods_ms(const ca_estimate_plan* p, float* kernel_ms) {

@@ -146,6 +146,13 @@ def load() -> C.CDLL:
         "ca_multi_estimate_plan_run": ([vp, vp, p(i32), vp, vp, vp], C.c_int),
         "ca_multi_estimate_plan_stats": ([vp, p(i32), p(i32), vp, i32], C.c_int),
         "ca_multi_estimate_plan_rerun_units": ([vp, p(i32)], C.c_int),
+        "ca_multi_estimate_plan_option_sums": ([vp, vp, vp], C.c_int),
+        "ca_multi_estimate_plan_option_price_sums": ([vp, vp, i32, vp], C.c_int),
+        "ca_multi_estimate_plan_fetch_group": ([vp, i32, vp, i32, p(i32)], C.c_int),
+        "ca_multi_estimate_plan_fetch": ([vp, vp], C.c_int),
+        "ca_multi_estimate_plan_groups_missing_pods": ([vp, i32, vp, i32, vp, vp], C.c_int),
+        "ca_multi_estimate_plan_reader_ms": ([vp, i32, vp, i32], C.c_int),
+        "ca_multi_estimate_plan_export_stats": ([vp, p(C.c_int64), p(i32)], C.c_int),
         "ca_multi_estimate_plan_destroy": ([vp], C.c_int),
         "ca_multi_estimate_batch": ([vp, vp, vp, vp, vp, i32, vp, p(i32), vp, vp, vp], C.c_int),
         "ca_multi_removal_plan_create": ([vp, vp, i32, vp, vp, vp, vp, p(vp)], C.c_int),
@@ -229,6 +236,10 @@ def exported_symbols() -> list[str]:
         "ca_util_table_update", "ca_util_table_set_added", "ca_multi_create", "ca_multi_destroy",
         "ca_multi_estimate_plan_create", "ca_multi_estimate_plan_run",
         "ca_multi_estimate_plan_stats", "ca_multi_estimate_plan_rerun_units", "ca_multi_estimate_plan_destroy", "ca_multi_estimate_batch",
+        "ca_multi_estimate_plan_option_sums", "ca_multi_estimate_plan_option_price_sums",
+        "ca_multi_estimate_plan_fetch_group", "ca_multi_estimate_plan_fetch",
+        "ca_multi_estimate_plan_groups_missing_pods", "ca_multi_estimate_plan_reader_ms",
+        "ca_multi_estimate_plan_export_stats",
         "ca_multi_removal_plan_create", "ca_multi_removal_plan_run", "ca_multi_removal_plan_stats",
         "ca_multi_removal_plan_rerun_units", "ca_multi_removal_plan_timings",
         "ca_multi_removal_plan_destroy", "ca_multi_find_nodes_to_remove",
@@ -1222,9 +1233,20 @@ class MultiEstimatePlan:
         self.sched_node = self._pinned.array[n:]
         self.results = np.zeros(self.G, abi.ESTIMATE_RESULT_DTYPE)
 
-    def run(self, max_nodes: int, last_index: int = 0, want_nodes: bool = True, copy: bool = True) -> EstimateOutput:
+    READERS = {"sums": 0, "price": 1, "missing": 2}          # CA_MULTI_READER_*
+
+    def run(self, max_nodes: int, last_index: int = 0, want_nodes: bool = True, copy: bool = True,
+            device_results: bool = False) -> EstimateOutput:
+        """One Estimate batch over the blocks.  With device_results=True every block's lists stay
+        in its own device's memory (sched_pod / sched_node of the returned output are None) and
+        the readers below work until the next run; after any other run they raise CasimError
+        (CA_ESTATE)."""
         lim = abi.LimiterC(max_nodes, 0)
         li = C.c_int32(last_index)
+        if device_results:
+            _check(self.lib.ca_multi_estimate_plan_run(self.h, C.byref(lim), C.byref(li), ptr(self.results), None,
+                                                       None), "ca_multi_estimate_plan_run")
+            return EstimateOutput(_fast_copy(self.results) if copy else self.results, None, None, li.value)
         _check(self.lib.ca_multi_estimate_plan_run(self.h, C.byref(lim), C.byref(li), ptr(self.results),
                                                    ptr(self.sched_pod), ptr(self.sched_node) if want_nodes else None),
                "ca_multi_estimate_plan_run")
@@ -1240,6 +1262,76 @@ class MultiEstimatePlan:
         self.lib.ca_multi_estimate_plan_rerun_units(self.h, C.byref(ru))
         return {"blocks": nb.value, "reruns": rr.value, "block_first_group": first[: nb.value + 1].tolist(),
                 "rerun_groups": ru.value}
+
+    # The readers of EstimatePlan, same names and return shapes, over the blocks of the last
+    # resident run (expander.DeviceOptions and nodegroupset.filter_plan_groups_by_pods take
+    # either plan).  A group that is not CA_OK in that run's results reads as an empty list.
+    def fetch(self) -> np.ndarray:
+        """All lists in the group_off layout; -1 behind n_scheduled and in groups that are not
+        CA_OK."""
+        out = np.full(max(self.total, 1), -1, np.int32)
+        _check(self.lib.ca_multi_estimate_plan_fetch(self.h, ptr(out)), "ca_multi_estimate_plan_fetch")
+        return out[: self.total]
+
+    def option_sums(self) -> tuple:
+        """EstimatePlan.option_sums over the blocks: (milli cpu [G], memory [G]) int64."""
+        cpu, mem = np.zeros(max(self.G, 1), np.int64), np.zeros(max(self.G, 1), np.int64)
+        _check(self.lib.ca_multi_estimate_plan_option_sums(self.h, ptr(cpu), ptr(mem)),
+               "ca_multi_estimate_plan_option_sums")
+        return cpu[: self.G], mem[: self.G]
+
+    def option_price_sums(self, pod_price) -> np.ndarray:
+        """EstimatePlan.option_price_sums over the blocks: one price per pod of the plan's pod
+        table, [G] float64, the reference's in-order sums bit for bit."""
+        price = np.ascontiguousarray(pod_price, dtype=np.float64)
+        if price.ndim != 1:
+            raise ValueError("pod_price: one value per pod of the pod set")
+        out = np.zeros(max(self.G, 1), np.float64)
+        _check(self.lib.ca_multi_estimate_plan_option_price_sums(self.h, ptr(price), len(price), ptr(out)),
+               "ca_multi_estimate_plan_option_price_sums")
+        return out[: self.G]
+
+    def fetch_group(self, g: int) -> np.ndarray:
+        """The scheduled pods of (global) group `g` of the last run, from its block's device."""
+        cap = int(self.group_off[g + 1] - self.group_off[g]) if 0 <= g < self.G else 0
+        out = np.full(max(cap, 1), -1, np.int32)
+        n = C.c_int32(0)
+        _check(self.lib.ca_multi_estimate_plan_fetch_group(self.h, g, ptr(out), cap, C.byref(n)),
+               "ca_multi_estimate_plan_fetch_group")
+        return out[: n.value]
+
+    def groups_missing_pods(self, required: int, groups) -> tuple:
+        """EstimatePlan.groups_missing_pods with global group indices.  The required list is
+        copied to the other blocks' devices (through host memory) only when a candidate outside
+        the required group's block needs it: export_stats() says what moved."""
+        gs = np.ascontiguousarray(groups, dtype=np.int32)
+        n_missing, first = np.zeros(max(len(gs), 1), np.int32), np.full(max(len(gs), 1), -1, np.int32)
+        _check(self.lib.ca_multi_estimate_plan_groups_missing_pods(self.h, int(required), ptr(gs), len(gs),
+                                                                   ptr(n_missing), ptr(first)),
+               "ca_multi_estimate_plan_groups_missing_pods")
+        return n_missing[: len(gs)], first[: len(gs)]
+
+    def reader_ms(self, which) -> np.ndarray:
+        """Per block, the device time (ms) of the kernels of the last call of reader `which`
+        ("sums", "price", "missing" or its CA_MULTI_READER_* number); 0 where a block launched
+        nothing."""
+        w = self.READERS[which] if isinstance(which, str) else int(which)
+        if w not in self.READERS.values():
+            raise ValueError(f"reader_ms: unknown reader {which!r}")
+        nb = C.c_int32(0)
+        _check(self.lib.ca_multi_estimate_plan_stats(self.h, C.byref(nb), None, None, 0),
+               "ca_multi_estimate_plan_stats")
+        ms = np.zeros(max(nb.value, 1), np.float32)
+        self.lib.ca_multi_estimate_plan_reader_ms(self.h, w, ptr(ms), nb.value)     # (returns the block count)
+        return ms[: nb.value]
+
+    def export_stats(self) -> dict:
+        """The last groups_missing_pods call's exchange: bytes of the required list that left its
+        device, and the blocks that uploaded it."""
+        b, n = C.c_int64(0), C.c_int32(0)
+        _check(self.lib.ca_multi_estimate_plan_export_stats(self.h, C.byref(b), C.byref(n)),
+               "ca_multi_estimate_plan_export_stats")
+        return {"exported_bytes": b.value, "importing_blocks": n.value}
 
     def close(self) -> None:
         if self.h:

@@ -256,7 +256,9 @@ def filter_node_groups_by_pods(groups: list, pods_required: list, options: dict)
 def filter_plan_groups_by_pods(plan, required: int, groups) -> list:
     """The device form: `required` and `groups` are group indices of an Estimate plan whose last
     run left its lists in device memory (every group in `groups` has an option).  Returns the
-    indices whose list holds every pod of `required`'s list, in input order."""
+    indices whose list holds every pod of `required`'s list, in input order.  `plan` is a
+    native.EstimatePlan or a native.MultiEstimatePlan after a resident run (global indices; the
+    required list is copied to another device only where a group of `groups` lies there)."""
     groups = [int(g) for g in groups]
     if not groups:
         return []

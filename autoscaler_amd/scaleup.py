@@ -20,6 +20,7 @@ here are in first-occurrence order, so an option's pods are in a canonical order
 """
 from __future__ import annotations
 
+from contextlib import contextmanager
 from dataclasses import dataclass, field
 
 import numpy as np
@@ -115,40 +116,37 @@ def ComputeExpansionOptions(snapshot: ClusterSnapshot, checker: SchedulerBasedPr
     return options, feas
 
 
-def ComputeBestExpansionOption(snapshot: ClusterSnapshot, checker: SchedulerBasedPredicateChecker,  # noqa: N802
-                               pod_groups: list, node_groups: list, limiter: ThresholdBasedEstimationLimiter,
-                               strategy):
-    """ComputeExpansionOptions followed by the orchestrator's option filter and
-    ExpanderStrategy.BestOption (orchestrator.go:139-195), with the options' pod lists left
-    in device memory: one Estimate plan run with device results, the `len(Pods) > 0 &&
-    NodeCount > 0` filter (:174) on its counts, `strategy` (an expander.ChainStrategy) on
-    the device form of its filters, and one copy of the pod list of each option that is left
-    (one option unless the chain fell through to the fallback).  Returns (the best
-    ExpansionOption or None, the feasibility matrix); the snapshot's backend must be the
-    device mirror."""
+@contextmanager
+def _resident_estimate(snapshot: ClusterSnapshot, checker: SchedulerBasedPredicateChecker,
+                       limiter: ThresholdBasedEstimationLimiter, node_groups: list, est_groups: list,
+                       est_index: list, all_pods: list, pod_idx, offs, multi):
+    """What ComputeBestExpansionOption and ComputeBalancedScaleUp share after the feasibility
+    matrix: the Estimate plan over `all_pods` (group g's pods are pod_idx[offs[g]:offs[g + 1]]),
+    one run with the lists left in device memory, the checker's counters, the :174 filter and the
+    device form of the options.  The plan is an EstimatePlan on the snapshot's backend, or, with
+    `multi` (a native.Multi), a MultiEstimatePlan over its mirrors, each of which is first made to
+    hold the snapshot (ClusterSnapshot.sync_replica).  Yields (plan, run output, valid group
+    indices, DeviceOptions, node infos by node group id); the plan is closed on exit."""
     from . import native
     from .expander import DeviceOptions, resources_for_node
     from .predicatechecker import unsupported
     from .scope import UnsupportedByKernels, out_of_scope_reason
 
-    if not isinstance(snapshot.backend, native.Mirror):
-        raise TypeError("ComputeBestExpansionOption reads the Estimate plan's device-resident lists: "
-                        "the snapshot's backend must be native.Mirror")
-    est_groups, est_index, feas = _feasible_pods(snapshot, pod_groups, node_groups)
-    if not est_groups:
-        return None, feas
-    all_pods, offs = [], [0]
-    for pods, _ in est_groups:
-        all_pods.extend(pods)
-        offs.append(len(all_pods))
     table = snapshot.interner.encode_pods(all_pods)
     templates = np.zeros(len(est_groups), abi.TEMPLATE_DTYPE)
     for g, (_, info) in enumerate(est_groups):
         templates[g] = snapshot.interner.encode_template(info.node, list(info.pods))
     caps = [resources_for_node(info.node) for _, info in est_groups]
     with unsupported("Estimate: the snapshot holds a pod with required anti-affinity"):
-        plan = native.EstimatePlan(snapshot.backend, table, np.array(offs, np.int32),
-                                   np.arange(len(all_pods), dtype=np.int32), templates)
+        if multi is None:
+            plan = native.EstimatePlan(snapshot.backend, table, np.array(offs, np.int32),
+                                       np.array(pod_idx, np.int32), templates)
+        else:
+            for m in multi.mirrors:            # (after _feasible_pods, which may have re-interned and replayed)
+                snapshot.sync_replica(m)
+            plan = native.MultiEstimatePlan(multi, table, np.array(offs, np.int32), np.array(pod_idx, np.int32),
+                                            templates)
+    node_infos = {(ng.Id() if hasattr(ng, "Id") else ng): info for ng, info in node_groups}
     with plan:
         with unsupported("Estimate: the snapshot holds a pod with required anti-affinity"):
             out = plan.run(limiter.max_nodes, checker.last_index, device_results=True)
@@ -161,8 +159,40 @@ def ComputeBestExpansionOption(snapshot: ClusterSnapshot, checker: SchedulerBase
         checker.last_index = out.last_index
         valid = [g for g, r in enumerate(out.results) if int(r["n_scheduled"]) > 0 and int(r["node_count"]) > 0]
         dev = DeviceOptions(plan, out.results, [c for c, _ in caps], [m for _, m in caps], pods=all_pods,
-                            node_groups=[node_groups[k][0] for k in est_index],
-                            node_infos={(ng.Id() if hasattr(ng, "Id") else ng): info for ng, info in node_groups})
+                            node_groups=[node_groups[k][0] for k in est_index], node_infos=node_infos)
+        yield plan, out, valid, dev, node_infos
+
+
+def _backend_must_be_mirror(snapshot: ClusterSnapshot, who: str) -> None:
+    from . import native
+    if not isinstance(snapshot.backend, native.Mirror):
+        raise TypeError(f"{who} reads the Estimate plan's device-resident lists: "
+                        "the snapshot's backend must be native.Mirror")
+
+
+def ComputeBestExpansionOption(snapshot: ClusterSnapshot, checker: SchedulerBasedPredicateChecker,  # noqa: N802
+                               pod_groups: list, node_groups: list, limiter: ThresholdBasedEstimationLimiter,
+                               strategy, multi=None):
+    """ComputeExpansionOptions followed by the orchestrator's option filter and
+    ExpanderStrategy.BestOption (orchestrator.go:139-195), with the options' pod lists left
+    in device memory: one Estimate plan run with device results, the `len(Pods) > 0 &&
+    NodeCount > 0` filter (:174) on its counts, `strategy` (an expander.ChainStrategy) on
+    the device form of its filters, and one copy of the pod list of each option that is left
+    (one option unless the chain fell through to the fallback).  Returns (the best
+    ExpansionOption or None, the feasibility matrix); the snapshot's backend must be the
+    device mirror.  `multi` (a native.Multi): the Estimate plan is sharded over its mirrors,
+    which are synced to the snapshot first; the feasibility matrix still runs on the backend and
+    everything after the run is the same code."""
+    _backend_must_be_mirror(snapshot, "ComputeBestExpansionOption")
+    est_groups, est_index, feas = _feasible_pods(snapshot, pod_groups, node_groups)
+    if not est_groups:
+        return None, feas
+    all_pods, offs = [], [0]
+    for pods, _ in est_groups:
+        all_pods.extend(pods)
+        offs.append(len(all_pods))
+    with _resident_estimate(snapshot, checker, limiter, node_groups, est_groups, est_index, all_pods,
+                            np.arange(len(all_pods), dtype=np.int32), offs, multi) as (plan, out, valid, dev, node_infos):
         if not valid:                      # "No expansion options" (orchestrator.go:181-188)
             return None, feas
         options = []
@@ -172,13 +202,12 @@ def ComputeBestExpansionOption(snapshot: ClusterSnapshot, checker: SchedulerBase
             options.append(ExpansionOption(ng, int(out.results[g]["node_count"]), pods))
     if len(options) == 1:
         return options[0], feas
-    node_infos = {(ng.Id() if hasattr(ng, "Id") else ng): info for ng, info in node_groups}
     return strategy.fallback.BestOption(options, node_infos), feas
 
 
 def ComputeBalancedScaleUp(snapshot: ClusterSnapshot, checker: SchedulerBasedPredicateChecker,  # noqa: N802
                            pod_groups: list, node_groups: list, limiter: ThresholdBasedEstimationLimiter,
-                           strategy, processor, cap_new_nodes=None):
+                           strategy, processor, cap_new_nodes=None, multi=None):
     """ScaleUp from the options to the final scale-up plan (orchestrator.go:139-313) with
     --balance-similar-node-groups, the options' pod lists left in device memory: the
     feasibility matrix; ONE Estimate plan over a shared pod table (every pending pod encoded
@@ -191,16 +220,12 @@ def ComputeBalancedScaleUp(snapshot: ClusterSnapshot, checker: SchedulerBasedPre
     on the device: nodegroupset.filter_plan_groups_by_pods);
     `processor.BalanceScaleUpBetweenGroups([best] + kept, new_nodes)`; one copy of the winner's
     list.  The node groups are objects with Id() / TargetSize() / MaxSize().  Returns (the best
-    ExpansionOption or None, [ScaleUpInfo], the feasibility matrix)."""
-    from . import native
-    from .expander import DeviceOptions, resources_for_node
+    ExpansionOption or None, [ScaleUpInfo], the feasibility matrix).  `multi`: as on
+    ComputeBestExpansionOption; the winner's list then crosses devices only if a similar group's
+    option lies in another block (casim.h, ca_multi_estimate_plan_groups_missing_pods)."""
     from .nodegroupset import filter_plan_groups_by_pods
-    from .predicatechecker import unsupported
-    from .scope import UnsupportedByKernels, out_of_scope_reason
 
-    if not isinstance(snapshot.backend, native.Mirror):
-        raise TypeError("ComputeBalancedScaleUp reads the Estimate plan's device-resident lists: "
-                        "the snapshot's backend must be native.Mirror")
+    _backend_must_be_mirror(snapshot, "ComputeBalancedScaleUp")
     est_groups, est_index, feas = _feasible_pods(snapshot, pod_groups, node_groups)
     if not est_groups:
         return None, [], feas
@@ -213,30 +238,10 @@ def ComputeBalancedScaleUp(snapshot: ClusterSnapshot, checker: SchedulerBasedPre
                 all_pods.append(p)
             pod_idx.append(row[id(p)])
         offs.append(len(pod_idx))
-    table = snapshot.interner.encode_pods(all_pods)
-    templates = np.zeros(len(est_groups), abi.TEMPLATE_DTYPE)
-    for g, (_, info) in enumerate(est_groups):
-        templates[g] = snapshot.interner.encode_template(info.node, list(info.pods))
-    caps = [resources_for_node(info.node) for _, info in est_groups]
-    with unsupported("Estimate: the snapshot holds a pod with required anti-affinity"):
-        plan = native.EstimatePlan(snapshot.backend, table, np.array(offs, np.int32), np.array(pod_idx, np.int32),
-                                   templates)
-    node_infos = {ng.Id(): info for ng, info in node_groups}
-    with plan:
-        with unsupported("Estimate: the snapshot holds a pod with required anti-affinity"):
-            out = plan.run(limiter.max_nodes, checker.last_index, device_results=True)
-        for g, r in enumerate(out.results):
-            if int(r["status"]) == abi.CA_EUNSUPPORTED:
-                why = next((out_of_scope_reason(p) for p in est_groups[g][0] if out_of_scope_reason(p)), None)
-                raise UnsupportedByKernels(f"node group {g}: " + (why or "pods depend on node identity (hostname / "
-                                                                          "nodeName) or template pods need InterPodAffinity"))
-            checker.evals += int(r["evals"])
-        checker.last_index = out.last_index
-        valid = [g for g, r in enumerate(out.results) if int(r["n_scheduled"]) > 0 and int(r["node_count"]) > 0]
+    with _resident_estimate(snapshot, checker, limiter, node_groups, est_groups, est_index, all_pods, pod_idx, offs,
+                            multi) as (plan, out, valid, dev, node_infos):
         if not valid:                      # "No expansion options" (orchestrator.go:181-188)
             return None, [], feas
-        dev = DeviceOptions(plan, out.results, [c for c, _ in caps], [m for _, m in caps], pods=all_pods,
-                            node_groups=[node_groups[k][0] for k in est_index], node_infos=node_infos)
         group_of = {node_groups[est_index[g]][0].Id(): g for g in valid}      # expansionOptions' keys
 
         def option(g):

@@ -791,14 +791,80 @@ int ca_multi_destroy(ca_multi* mm);   /* the mirrors stay the caller's */
 int ca_multi_reorder_nodes(ca_multi* mm, const int32_t* order, int32_t n);   /* every mirror; all or none */
 
 /* Estimate batch (ca_estimate_batch semantics, prefix protocol included) over the mirrors'
- * blocks of node groups.  sched_pod is required (host memory; page-locked memory from
- * ca_host_alloc lets each block publish zero-copy); sched_node may be NULL. */
+ * blocks of node groups.  sched_pod is host memory (page-locked memory from ca_host_alloc
+ * lets each block publish zero-copy); sched_node may be NULL.  ca_multi_estimate_batch
+ * requires sched_pod. */
 typedef struct ca_multi_estimate_plan ca_multi_estimate_plan;
 int ca_multi_estimate_plan_create(ca_multi* mm, const ca_pod_table* t, const int32_t* group_off,
                                   const int32_t* pod_idx, const ca_template* templates, int32_t n_groups,
                                   ca_multi_estimate_plan** out);
 int ca_multi_estimate_plan_run(ca_multi_estimate_plan* p, const ca_limiter* limiter, int32_t* last_index,
                                ca_estimate_result* results, int32_t* sched_pod, int32_t* sched_node);
+/* sched_pod == NULL (and sched_node == NULL; sched_node without sched_pod is CA_EINVAL) is a
+ * resident run, as on ca_estimate_plan_run: every block's plan runs with sched_pod == NULL,
+ * results[] and *last_index are returned exactly as a host-list run returns them (a re-run of
+ * a lastIndex-sensitive block is a resident run too), and every block's lists stay in its own
+ * plan, on its own device, until the next run.
+ *
+ * State.  The readers below work after a resident run that returned CA_OK and return
+ * CA_ESTATE otherwise: before any run, after a host-list run, after a run that failed.  The
+ * caller decides by the argument; how a block's results reached the host plays no part (it
+ * does on ca_estimate_plan_option_sums).
+ *
+ * The sharded plan's results[] of that run are authoritative: a group whose status there is
+ * not CA_OK (CA_EUNSUPPORTED, CA_ENOTRUN, every group of a block behind a prefix cut — such a
+ * block did run on its device) has n_scheduled 0 for every reader, whatever its block's plan
+ * holds.  A block without a CA_OK group launches nothing.
+ *
+ * All readers take global group indices and write arrays in the caller's layout (G entries, or
+ * group_off positions).  The blocks work concurrently; the first failing block's status is
+ * returned and then the outputs mean nothing. */
+/* ca_estimate_plan_option_sums over the blocks: resourcesForPods of every option, G values
+ * each; a group that is not CA_OK sums to 0.  G == 0: CA_OK without a launch. */
+int ca_multi_estimate_plan_option_sums(ca_multi_estimate_plan* p, int64_t* req_milli_cpu, int64_t* req_memory);
+/* ca_estimate_plan_option_price_sums over the blocks, bit for bit the in-order float64 sum
+ * documented there.  Every block's pod set is built from the plan's one pod table, so one
+ * price table indexed by pod-set index (n_prices = the table's pod count, else CA_EINVAL)
+ * serves all blocks; it is uploaded to every block with a CA_OK group on each call.  +0.0 for a
+ * group that is not CA_OK. */
+int ca_multi_estimate_plan_option_price_sums(ca_multi_estimate_plan* p, const double* pod_price,
+                                             int32_t n_prices, double* total_pod_price);
+/* ca_estimate_plan_fetch_group by global group index: *n = n_scheduled (0 for a group that is
+ * not CA_OK, nothing copied), one D2H from the group's device; CA_ECAPACITY when cap is short
+ * (nothing copied). */
+int ca_multi_estimate_plan_fetch_group(const ca_multi_estimate_plan* p, int32_t group, int32_t* sched_pod,
+                                       int32_t cap, int32_t* n);
+/* All lists in the caller's group_off layout (group_off[G] ids, one D2H per block with a CA_OK
+ * group).  Unlike ca_estimate_plan_fetch, positions from n_scheduled on, and every position
+ * of a group that is not CA_OK, read -1. */
+int ca_multi_estimate_plan_fetch(const ca_multi_estimate_plan* p, int32_t* sched_pod);
+/* filterNodeGroupsByPods on the resident lists of a sharded run: the contract of
+ * ca_estimate_plan_groups_missing_pods word for word (the slots the lengths answer, repeated
+ * groups, required_group among the candidates, NULL first_missing, CA_EINVAL / CA_EDEVICE /
+ * CA_ECAPACITY; the scratch bound applies to each block's rows on its own), with n_scheduled
+ * as defined above.  Pods are compared by index into the plan's one pod table.
+ * This is the one call in which list data crosses devices.  The block that holds
+ * required_group answers its own candidates as the one-device call does.  If a candidate in
+ * another block needs a bitmap row, the n_scheduled counted ids of the required list are
+ * copied once to page-locked memory of the sharded plan (one stream-ordered D2H, 4 bytes per
+ * id), and each such block uploads them to scratch of its own and tests its rows against
+ * them with the same kernels.  No peer-to-peer copy is made and no peer access is needed.  If
+ * every such candidate is in the owner's block, nothing leaves its device. */
+int ca_multi_estimate_plan_groups_missing_pods(ca_multi_estimate_plan* p, int32_t required_group,
+                                               const int32_t* groups, int32_t n_groups,
+                                               int32_t* n_missing, int32_t* first_missing);
+#define CA_MULTI_READER_SUMS    0   /* ca_multi_estimate_plan_option_sums        */
+#define CA_MULTI_READER_PRICE   1   /* ca_multi_estimate_plan_option_price_sums  */
+#define CA_MULTI_READER_MISSING 2   /* ca_multi_estimate_plan_groups_missing_pods */
+/* Per block, the device time (HIP events, ms) of the kernels of the last call of reader
+ * `which` (the block plan's own *_ms), 0 for a block that launched nothing in that call.
+ * Writes min(cap, blocks) values and returns the block count (a count, not a status;
+ * ca_multi_estimate_plan_stats reports the same count).  An unknown `which`: CA_EINVAL. */
+int ca_multi_estimate_plan_reader_ms(const ca_multi_estimate_plan* p, int32_t which, float* ms, int32_t cap);
+/* The exchange of the last ca_multi_estimate_plan_groups_missing_pods call: bytes of the
+ * required list exported from its device (0: nothing crossed), and the blocks that uploaded
+ * it.  Either pointer may be NULL. */
+int ca_multi_estimate_plan_export_stats(const ca_multi_estimate_plan* p, int64_t* bytes, int32_t* blocks);
 /* blocks, re-runs of the last run, and the first group of each block (n_blocks + 1 values) */
 int ca_multi_estimate_plan_stats(const ca_multi_estimate_plan* p, int32_t* n_blocks, int32_t* reruns,
                                  int32_t* block_first_group, int32_t cap);
