@@ -18,6 +18,10 @@ CA_OK, CA_EINVAL, CA_ENOTFOUND, CA_EEXISTS, CA_EDEVICE, CA_ECAPACITY, CA_EUNSUPP
 
 CA_EXPANDER_MOST_PODS, CA_EXPANDER_LEAST_WASTE = 1, 2     # ca_expander_best_options filters
 
+# k_option_lists (estimate.hip OPT_TILE / OPT_CHUNK): output positions of one group per
+# workgroup, and pod equivalence groups per partial sum (tests place their cases at both)
+OPTION_LIST_TILE, OPTION_LIST_CHUNK = 2048, 256
+
 CA_MAX_SCALAR = 8
 CA_LABEL_WORDS = 4
 CA_PORT_WORDS = 2

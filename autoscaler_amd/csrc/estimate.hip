@@ -172,6 +172,98 @@ __global__ void __launch_bounds__(256) k_item_cls(const int32_t* __restrict__ po
     for (int32_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) out[i] = cls[pod_idx[i]];
 }
 
+// The lists from the option matrix (ca_estimate_plan_create_options; DESIGN.md §4 "lists
+// from the option matrix").  Group g's list is the concatenation, for e ascending with
+// ok[g][e] != 0, of equivalence group e's pods eg_pod[eg_off[e] .. eg_off[e+1])
+// (ComputeExpansionOption's append, orchestrator.go:468-482).  No [G][n_eg] table of list
+// offsets is kept (with one pod per equivalence group it would be as large as the lists):
+// k_option_chunks leaves, per row, the list offset at which every chunk of OPT_CHUNK
+// equivalence groups starts, and k_option_lists redoes the scan inside a chunk in LDS.
+constexpr int OPT_TILE = 2048;     // output positions of one group per workgroup (abi.OPTION_LIST_TILE)
+constexpr int OPT_CHUNK = 256;     // equivalence groups per partial sum (abi.OPTION_LIST_CHUNK)
+
+// inclusive scan of one value per thread over a 256-thread block (wsum: 4 words of LDS; the
+// caller's next barrier separates two scans)
+__device__ inline int32_t block_scan_256(int32_t v, int32_t* wsum) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int32_t x = v;
+    for (int o = 1; o < 64; o <<= 1) {
+        const int32_t y = __shfl_up(x, o, 64);
+        if (lane >= o) x += y;
+    }
+    if (lane == 63) wsum[w] = x;
+    __syncthreads();
+    for (int q = 0; q < w; q++) x += wsum[q];
+    return x;
+}
+
+// one workgroup per row: chunk_pre[g][k] = list offset of the first pod of chunk k
+__global__ void __launch_bounds__(256) k_option_chunks(const int32_t* __restrict__ eg_off, const uint8_t* __restrict__ ok,
+                                                      int32_t n_eg, int32_t nch, int32_t* __restrict__ chunk_pre) {
+    __shared__ int32_t wsum[4];
+    const uint8_t* row = ok + (size_t)blockIdx.x * (size_t)n_eg;
+    int32_t* pre = chunk_pre + (size_t)blockIdx.x * (size_t)nch;
+    int32_t running = 0;
+    for (int32_t k = 0; k < nch; k++) {
+        const int32_t e = k * OPT_CHUNK + (int32_t)threadIdx.x;
+        const int32_t len = (e < n_eg && row[e]) ? eg_off[e + 1] - eg_off[e] : 0;
+        (void)block_scan_256(len, wsum);
+        if (threadIdx.x == 0) pre[k] = running;
+        running += wsum[0] + wsum[1] + wsum[2] + wsum[3];      // the chunk's total
+        __syncthreads();
+    }
+}
+
+// One workgroup per OPT_TILE output positions of one group (as k_copy_segments): a binary
+// search of the row's chunk offsets for the chunk holding the first position, then chunk
+// after chunk: the passing groups' lengths are scanned in LDS, and every output position
+// finds its equivalence group there (8 LDS probes) — consecutive threads write consecutive
+// positions, and read consecutive eg_pod entries inside a segment.  The score class is
+// gathered beside the pod id (item_cls != NULL: the bucket path).
+__global__ void __launch_bounds__(256) k_option_lists(const GroupMeta* __restrict__ groups,
+                                                     const int32_t* __restrict__ eg_off, const int32_t* __restrict__ eg_pod,
+                                                     const uint8_t* __restrict__ ok, int32_t n_eg, int32_t nch,
+                                                     const int32_t* __restrict__ chunk_pre, const int32_t* __restrict__ cls,
+                                                     int32_t* __restrict__ pod_idx, int32_t* __restrict__ item_cls) {
+    __shared__ int32_t s_end[OPT_CHUNK], s_delta[OPT_CHUNK], wsum[4];
+    const GroupMeta gm = groups[blockIdx.y];
+    const int32_t base = (int32_t)blockIdx.x * OPT_TILE;
+    if (base >= gm.count) return;
+    const int32_t end = min(base + OPT_TILE, gm.count);
+    const uint8_t* row = ok + (size_t)blockIdx.y * (size_t)n_eg;
+    const int32_t* pre = chunk_pre + (size_t)blockIdx.y * (size_t)nch;
+    int32_t k0 = 0, hi = nch;                      // last chunk starting at or before base
+    while (hi - k0 > 1) {
+        const int32_t mid = (k0 + hi) >> 1;
+        if (pre[mid] <= base) k0 = mid; else hi = mid;
+    }
+    int32_t* dst = pod_idx + gm.off;
+    int32_t* dcl = item_cls ? item_cls + gm.off : nullptr;
+    for (int32_t k = k0; k < nch; k++) {
+        const int32_t cstart = pre[k];
+        if (cstart >= end) break;
+        const int32_t e = k * OPT_CHUNK + (int32_t)threadIdx.x;
+        int32_t src = 0, len = 0;
+        if (e < n_eg && row[e]) { src = eg_off[e]; len = eg_off[e + 1] - src; }
+        const int32_t x = block_scan_256(len, wsum);
+        s_end[threadIdx.x] = cstart + x;                       // list offset after group e
+        s_delta[threadIdx.x] = src - (cstart + x - len);       // eg_pod index of list position i: delta + i
+        __syncthreads();
+        const int32_t a = max(base, cstart), b = min(end, s_end[OPT_CHUNK - 1]);
+        for (int32_t i = a + (int32_t)threadIdx.x; i < b; i += 256) {
+            int32_t lo = 0, up = OPT_CHUNK - 1;                // first group ending after i (i < s_end[last])
+            while (lo < up) {
+                const int32_t mid = (lo + up) >> 1;
+                if (s_end[mid] > i) up = mid; else lo = mid + 1;
+            }
+            const int32_t pod = eg_pod[s_delta[lo] + i];
+            dst[i] = pod;
+            if (dcl) dcl[i] = cls[pod];
+        }
+        __syncthreads();
+    }
+}
+
 // 1. score + static predicates + tile sort ----------------------------------
 __global__ void __launch_bounds__(256) k_score_tiles(
     const GroupMeta* __restrict__ groups, const int32_t* __restrict__ pod_idx, const ca_template* __restrict__ tmpls,
@@ -2721,6 +2813,7 @@ struct ca_estimate_plan {
     DevBuf d_sortC, d_ids_ready, d_spod_go, d_crank2;
     DevBuf d_rstart, d_rsp;        // decoupled: per group, each rank's first stream position and record
     DevBuf d_item_cls;             // bucket path: the score class of every (group, pod) item, uploaded with the lists
+    float opt_lists_ms = 0.f;      // option form: device time of k_option_lists at creation (0 otherwise)
     int32_t ids_epoch = 0;
     // shared sorts (sort_classes): the number of sort classes — when below G their
     // representatives, in group order, follow the G records of d_meta as k_pdq_sort's group
@@ -2871,8 +2964,10 @@ namespace {
 // (binpacking_estimator.go:72-74, 164-193; same float64 operations as k_class_rank,
 // -ffp-contract=off).  Per group, the U class scores against the template are sorted;
 // only when a tie exists are the group's own classes looked up.
-bool groups_tie_free(const ca_podset* s, const int32_t* pod_idx, const std::vector<GroupMeta>& meta,
-                     const ca_template* templates) {
+// `mark(g, seen)` sets seen[c] = g for every class c of group g's list (walked only for a
+// group whose template has a tie).
+bool groups_tie_free(const ca_podset* s, const std::vector<GroupMeta>& meta, const ca_template* templates,
+                     const std::function<void(int32_t, std::vector<int32_t>&)>& mark) {
     const int32_t U = s->n_cls;
     if (U < 2) return true;
     std::vector<std::pair<uint64_t, int32_t>> key((size_t)U);
@@ -2900,7 +2995,7 @@ bool groups_tie_free(const ca_podset* s, const int32_t* pod_idx, const std::vect
             runs.push_back(key[i].second);
         }
         if (runs.empty()) continue;
-        for (int32_t i = meta[g].off; i < meta[g].off + meta[g].count; i++) seen[s->h_cls[pod_idx[i]]] = (int32_t)g;
+        mark((int32_t)g, seen);
         int32_t present = 0;
         for (size_t i = 0; i <= runs.size(); i++) {
             if (i == runs.size() || runs[i] < 0) { present = 0; continue; }
@@ -2920,9 +3015,16 @@ bool groups_tie_free(const ca_podset* s, const int32_t* pod_idx, const std::vect
 // a strided sample of the list) only groups the candidates, every match is a full
 // comparison of the lists.  The rank vectors cost G * U log U on the host, so a batch with
 // G * U above SHARE_MAX_GU keeps one sort per group.  `side` is run once, beside the
-// comparisons when they go to the host's workers.
+// comparisons when they go to the host's workers.  The lists are seen through `src`: a
+// signature per group, the exact comparison of two groups of equal count, and what one
+// comparison reads (the option form compares matrix rows instead of lists).
 constexpr int64_t SHARE_MAX_GU = 1 << 17;
-int32_t sort_classes(const ca_podset* s, const int32_t* pod_idx, const std::vector<GroupMeta>& meta,
+struct ListCompare {
+    std::function<uint64_t(int32_t)> sig;               // equal lists give equal signatures
+    std::function<bool(int32_t, int32_t)> same;         // the lists of two groups are element-wise equal
+    std::function<size_t(int32_t)> bytes;               // bytes one comparison against group g reads
+};
+int32_t sort_classes(const ca_podset* s, const ListCompare& src, const std::vector<GroupMeta>& meta,
                      const ca_template* templates, std::vector<int32_t>& rep, const std::function<void()>& side) {
     const int32_t G = (int32_t)meta.size(), U = s->n_cls;
     rep.resize((size_t)G);
@@ -2959,17 +3061,10 @@ int32_t sort_classes(const ca_podset* s, const int32_t* pod_idx, const std::vect
         by_alloc.emplace(std::make_pair(acpu, amem), id);
         rv[g] = id;
     }
-    // candidates: same count, same rank vector, same sample of the list
-    constexpr int32_t NS = 8;                         // (few: every sample of a cold list is a cache miss)
+    // candidates: same count, same rank vector, same signature of the list
     std::map<std::tuple<int32_t, int32_t, uint64_t>, std::vector<int32_t>> cand;
     for (int32_t g = 0; g < G; g++) {
-        const int32_t n = meta[g].count;
-        const int32_t* l = pod_idx + meta[g].off;
-        uint64_t h = 0x9E3779B97F4A7C15ull;
-        const int32_t step = std::max(1, n / NS);
-        for (int32_t i = 0; i < n; i += step) h = (h ^ (uint32_t)l[i]) * 0x100000001B3ull;
-        if (n > 0) h = (h ^ (uint32_t)l[n - 1]) * 0x100000001B3ull;
-        cand[std::make_tuple(n, rv[g], h)].push_back(g);
+        cand[std::make_tuple(meta[g].count, rv[g], src.sig(g))].push_back(g);
     }
     // the first group of a bucket is a representative; the others are compared with it, every
     // pair of every bucket in one pass over the host's workers (task 0 runs `side` first: the
@@ -2979,13 +3074,13 @@ int32_t sort_classes(const ca_podset* s, const int32_t* pod_idx, const std::vect
     size_t pair_bytes = 0;
     for (auto& kv : cand) {
         const std::vector<int32_t>& v = kv.second;        // (ascending group order)
-        const size_t bytes = sizeof(int32_t) * (size_t)std::get<0>(kv.first);
+        const size_t bytes = src.bytes(v[0]);
         for (size_t k = 1; k < v.size(); k++) { pairs.push_back({v[0], v[k], bytes}); pair_bytes += bytes; }
     }
     std::vector<uint8_t> same(pairs.size(), 0);
     auto compare = [&](size_t k) {
         const Pair& q = pairs[k];
-        same[k] = q.bytes == 0 || std::memcmp(pod_idx + meta[q.head].off, pod_idx + meta[q.g].off, q.bytes) == 0;
+        same[k] = meta[q.head].count == 0 || src.same(q.head, q.g);
     };
     if (pair_bytes < ((size_t)1 << 18)) {
         side();
@@ -3006,14 +3101,13 @@ int32_t sort_classes(const ca_podset* s, const int32_t* pod_idx, const std::vect
         std::vector<int32_t> v;
         for (size_t k = 0; k < kv.second.size(); k++)
             if (k == 0 || rep[kv.second[k]] == kv.second[k]) v.push_back(kv.second[k]);
-        const size_t bytes = sizeof(int32_t) * (size_t)std::get<0>(kv.first);
         classes++;                                        // (v[0] and the groups equal to it)
         v.erase(v.begin());
         while (!v.empty()) {
             classes++;
             std::vector<int32_t> rest;
             for (size_t k = 1; k < v.size(); k++) {
-                if (std::memcmp(pod_idx + meta[v[0]].off, pod_idx + meta[v[k]].off, bytes) == 0) rep[v[k]] = v[0];
+                if (meta[v[0]].count == 0 || src.same(v[0], v[k])) rep[v[k]] = v[0];
                 else rest.push_back(v[k]);
             }
             v.swap(rest);
@@ -3022,8 +3116,250 @@ int32_t sort_classes(const ca_podset* s, const int32_t* pod_idx, const std::vect
     return classes;
 }
 
+// What plan_prepare needs from the groups' lists, from either form of them: the sort classes,
+// the port / extended-resource flags, the summed requests and whether the decoupled Go order
+// is exact.  lists_from_host walks the caller's lists (and queues their upload);
+// lists_from_options derives the same per equivalence group and combines over the matrix rows.
+struct ListFacts {
+    std::vector<int32_t> sort_rep;            // empty: one sort per group
+    int32_t n_classes = 0;
+    std::vector<double> c, mm;                // per group: summed cpu / memory requests
+    bool tie_free = false;
+};
+
+// ca_estimate_plan_create_options' inputs (validated by the entry point)
+struct OptionSrc {
+    const int32_t* eg_off;
+    const int32_t* eg_pod;
+    int32_t n_eg;
+    const uint8_t* ok;
+};
+
+// shared sorts are looked for (CASIM_SORT_SHARE=0: one sort per group, for tests and A/B)
+bool sort_share_wanted(const ca_estimate_plan* p, const ca_podset* s) {
+    return p->bucket && s->cls_uniform && p->total > 0 &&
+           !(knob_env("CASIM_SORT_SHARE") && atoi(knob_env("CASIM_SORT_SHARE")) == 0);
+}
+
+int lists_from_host(ca_estimate_plan* p, const ca_podset* s, const int32_t* group_off, const int32_t* pod_idx,
+                    const ca_template* templates, int32_t G, hipStream_t st, ListFacts& lf) {
+    int rc;
+    const size_t tot = (size_t)std::max(p->total, 1);
+    // The sort classes first (sort_classes; CASIM_SORT_SHARE=0: one sort per group, for tests
+    // and A/B): groups with equal lists also share what the pass below finds, so it walks
+    // each class's first group only — a comparison of two lists costs far less per item than
+    // the walk's lookups.
+    std::vector<int32_t>& sort_rep = lf.sort_rep;
+    int32_t n_classes = G;
+    // (the list upload is queued by the caller's thread beside the comparisons, or beside the
+    // walk below when there are none)
+    hipError_t ce = hipSuccess;
+    rc = CA_OK;
+    bool uploaded = false;
+    auto upload = [&]() {
+        if ((rc = p->d_pod_idx.reserve(sizeof(int32_t) * tot)) == CA_OK && p->total)
+            ce = hipMemcpyAsync(p->d_pod_idx.ptr, pod_idx, sizeof(int32_t) * p->total, hipMemcpyHostToDevice, st);
+        uploaded = true;
+    };
+    if (sort_share_wanted(p, s)) {
+        // candidates by a strided sample of the list (few: every sample of a cold list is a
+        // cache miss), every match a full comparison
+        const std::vector<GroupMeta>& meta = p->h_meta;
+        ListCompare lc;
+        lc.sig = [&](int32_t g) {
+            constexpr int32_t NS = 8;
+            const int32_t n = meta[(size_t)g].count;
+            const int32_t* l = pod_idx + meta[(size_t)g].off;
+            uint64_t h = 0x9E3779B97F4A7C15ull;
+            const int32_t step = std::max(1, n / NS);
+            for (int32_t i = 0; i < n; i += step) h = (h ^ (uint32_t)l[i]) * 0x100000001B3ull;
+            if (n > 0) h = (h ^ (uint32_t)l[n - 1]) * 0x100000001B3ull;
+            return h;
+        };
+        lc.same = [&](int32_t a, int32_t b) {
+            return std::memcmp(pod_idx + meta[(size_t)a].off, pod_idx + meta[(size_t)b].off,
+                               sizeof(int32_t) * (size_t)meta[(size_t)a].count) == 0;
+        };
+        lc.bytes = [&](int32_t g) { return sizeof(int32_t) * (size_t)meta[(size_t)g].count; };
+        n_classes = sort_classes(s, lc, p->h_meta, templates, sort_rep, upload);
+    }
+    if (n_classes == G) sort_rep.clear();
+    lf.n_classes = n_classes;
+    // One pass over the lists (per-pod summaries of the podset: compact arrays instead of
+    // the 208-B records), split over host threads for big batches: index validation, the
+    // port / extended-resource flags and each group's summed requests for the demand
+    // order.  The lists travel to the device meanwhile (the caller's thread queues the copy);
+    // the item classes are gathered there from the podset's class column (k_item_cls).
+    {
+        // the groups walked and the prefix of their counts: the walk's items, split evenly
+        std::vector<int32_t> wg, woff(1, 0);
+        for (int32_t g = 0; g < G; g++)
+            if (sort_rep.empty() || sort_rep[g] == g) { wg.push_back(g); woff.push_back(woff.back() + p->h_meta[g].count); }
+        const int32_t K = (int32_t)wg.size(), wtotal = woff.back();
+        const int32_t T = std::max(1, std::min(7, wtotal / (1 << 17)));
+        struct Part { bool bad = false; uint8_t fl = 0; std::vector<double> c, mm; };
+        std::vector<Part> part((size_t)T);
+        const bool want_fl = s->any_ports || s->any_scalar;
+        auto work = [&](int32_t t) {
+            Part& pt = part[(size_t)t];
+            pt.c.assign((size_t)G, 0.0);
+            pt.mm.assign((size_t)G, 0.0);
+            const int32_t a = (int32_t)((int64_t)wtotal * t / T), b = (int32_t)((int64_t)wtotal * (t + 1) / T);
+            int32_t k0 = std::max(0, (int32_t)(std::upper_bound(woff.begin(), woff.end(), a) - woff.begin()) - 1);
+            const int32_t np_ = s->t.n_pods;
+            const int64_t* req = s->h_req.data();
+            for (int32_t v = a; v < b && !pt.bad;) {       // v: position in the walked groups' items
+                while (k0 < K - 1 && woff[(size_t)k0 + 1] <= v) k0++;
+                const int32_t g = wg[(size_t)k0];
+                const int32_t i = group_off[g] + (v - woff[(size_t)k0]);
+                const int32_t e = group_off[g] + (std::min(b, woff[(size_t)k0 + 1]) - woff[(size_t)k0]);
+                double c0 = 0, c1 = 0, m0 = 0, m1 = 0;   // (two chains each: the adds pipeline)
+                bool bad = false;
+                int32_t k = i;
+                for (; k + 1 < e; k += 2) {
+                    const int32_t p0 = pod_idx[k], p1 = pod_idx[k + 1];
+                    bad |= (uint32_t)p0 >= (uint32_t)np_ || (uint32_t)p1 >= (uint32_t)np_;
+                    if (bad) break;
+                    c0 += (double)req[2 * (size_t)p0]; m0 += (double)req[2 * (size_t)p0 + 1];
+                    c1 += (double)req[2 * (size_t)p1]; m1 += (double)req[2 * (size_t)p1 + 1];
+                }
+                if (!bad && k < e) {
+                    const int32_t p0 = pod_idx[k];
+                    bad = (uint32_t)p0 >= (uint32_t)np_;
+                    if (!bad) { c0 += (double)req[2 * (size_t)p0]; m0 += (double)req[2 * (size_t)p0 + 1]; }
+                }
+                if (bad) { pt.bad = true; break; }
+                if (want_fl)
+                    for (int32_t q = i; q < e; q++) pt.fl |= s->h_pflags[pod_idx[q]];
+                pt.c[(size_t)g] += c0 + c1;
+                pt.mm[(size_t)g] += m0 + m1;
+                v += e - i;
+            }
+        };
+        // task 0 (the caller's thread) queues the list upload if it is not queued yet,
+        // tasks 1..T walk the items
+        if (uploaded) casim::parallel_run(T, work);
+        else casim::parallel_run(T + 1, [&](int32_t t) { if (t > 0) work(t - 1); else upload(); });
+        if (rc != CA_OK) return rc;
+        CA_HIP_CHECK(ce);
+        bool bad = false;
+        std::vector<double>& c = lf.c;
+        std::vector<double>& mm = lf.mm;
+        c.assign((size_t)G, 0.0);
+        mm.assign((size_t)G, 0.0);
+        for (const Part& pt : part) {
+            bad |= pt.bad;
+            if (pt.fl & 1) p->use_ports = true;
+            if (pt.fl & 2) p->use_scalar = true;
+            for (int32_t g = 0; g < G; g++) { c[(size_t)g] += pt.c[(size_t)g]; mm[(size_t)g] += pt.mm[(size_t)g]; }
+        }
+        if (bad) {
+            CA_HIP_CHECK(hipStreamSynchronize(st));    // (the list copy may still read pod_idx)
+            return CA_EINVAL;
+        }
+        for (int32_t g = 0; g < G && !sort_rep.empty(); g++) {      // equal lists, equal sums
+            c[(size_t)g] = c[(size_t)sort_rep[g]];
+            mm[(size_t)g] = mm[(size_t)sort_rep[g]];
+        }
+    }
+    lf.tie_free = p->bucket && s->cls_uniform &&
+                  groups_tie_free(s, p->h_meta, templates, [&](int32_t g, std::vector<int32_t>& seen) {
+                      const GroupMeta& gm = p->h_meta[(size_t)g];
+                      for (int32_t i = gm.off; i < gm.off + gm.count; i++) seen[s->h_cls[pod_idx[i]]] = g;
+                  });
+    return CA_OK;
+}
+
+// The same facts without the lists.  Every one of them is a per-equivalence-group quantity
+// combined over a matrix row: each group is walked once (O(pending pods)), then the rows are
+// combined in O(G * n_eg).  An empty equivalence group adds nothing to a list, so it counts as
+// failing everywhere: two rows then give equal lists exactly when they agree on every
+// non-empty group (the groups are disjoint), which is what the sort classes compare.  The
+// float64 request sums are taken in another order than the item walk's; they only feed the
+// demand order, which no result depends on.
+int lists_from_options(ca_estimate_plan* p, const ca_podset* s, const OptionSrc& o, const ca_template* templates,
+                       int32_t G, ListFacts& lf) {
+    const int32_t E = o.n_eg, U = s->n_cls;
+    const bool want_fl = s->any_ports || s->any_scalar;
+    const bool want_cls = p->bucket && s->cls_uniform && U >= 2;          // (groups_tie_free's readers)
+    std::vector<int32_t> len((size_t)E), cl_off(1, 0), cl, stamp(want_cls ? (size_t)U : 0, -1);
+    std::vector<uint8_t> fl((size_t)E, 0);
+    std::vector<double> ec((size_t)E), em((size_t)E);
+    const int64_t* req = s->h_req.data();
+    for (int32_t e = 0; e < E; e++) {
+        const int32_t a = o.eg_off[e], b = o.eg_off[e + 1];
+        len[(size_t)e] = b - a;
+        double c0 = 0, m0 = 0;
+        uint8_t f = 0;
+        for (int32_t i = a; i < b; i++) {
+            const size_t pod = (size_t)o.eg_pod[i];
+            c0 += (double)req[2 * pod];
+            m0 += (double)req[2 * pod + 1];
+            if (want_fl) f |= s->h_pflags[pod];
+            if (want_cls) {
+                const int32_t c = s->h_cls[pod];
+                if (stamp[(size_t)c] != e) { stamp[(size_t)c] = e; cl.push_back(c); }
+            }
+        }
+        ec[(size_t)e] = c0; em[(size_t)e] = m0; fl[(size_t)e] = f;
+        cl_off.push_back((int32_t)cl.size());
+    }
+    lf.c.assign((size_t)G, 0.0);
+    lf.mm.assign((size_t)G, 0.0);
+    std::vector<uint64_t> sig((size_t)G);
+    const int32_t T = (int32_t)std::max<int64_t>(1, std::min<int64_t>(std::min(7, G), (int64_t)G * E / (1 << 19)));
+    std::vector<uint8_t> tfl((size_t)T, 0);
+    casim::parallel_run(T, [&](int32_t t) {
+        uint8_t f = 0;
+        for (int32_t g = (int32_t)((int64_t)G * t / T); g < (int32_t)((int64_t)G * (t + 1) / T); g++) {
+            const uint8_t* row = o.ok + (size_t)g * (size_t)E;
+            double c = 0, m = 0;
+            uint64_t h = 0x9E3779B97F4A7C15ull;
+            for (int32_t e = 0; e < E; e++)
+                if (row[e] && len[(size_t)e]) {
+                    c += ec[(size_t)e]; m += em[(size_t)e]; f |= fl[(size_t)e];
+                    h = (h ^ (uint32_t)e) * 0x100000001B3ull;
+                }
+            lf.c[(size_t)g] = c; lf.mm[(size_t)g] = m; sig[(size_t)g] = h;
+        }
+        tfl[(size_t)t] = f;
+    });
+    for (uint8_t f : tfl) {
+        if (f & 1) p->use_ports = true;
+        if (f & 2) p->use_scalar = true;
+    }
+    int32_t n_classes = G;
+    if (sort_share_wanted(p, s)) {
+        ListCompare lc;
+        lc.sig = [&](int32_t g) { return sig[(size_t)g]; };
+        lc.same = [&](int32_t a, int32_t b) {
+            const uint8_t* ra = o.ok + (size_t)a * (size_t)E;
+            const uint8_t* rb = o.ok + (size_t)b * (size_t)E;
+            for (int32_t e = 0; e < E; e++)
+                if (((ra[e] != 0) != (rb[e] != 0)) && len[(size_t)e]) return false;
+            return true;
+        };
+        lc.bytes = [&](int32_t) { return (size_t)E; };
+        n_classes = sort_classes(s, lc, p->h_meta, templates, lf.sort_rep, []() {});
+    }
+    if (n_classes == G) lf.sort_rep.clear();
+    lf.n_classes = n_classes;
+    lf.tie_free = p->bucket && s->cls_uniform &&
+                  groups_tie_free(s, p->h_meta, templates, [&](int32_t g, std::vector<int32_t>& seen) {
+                      const uint8_t* row = o.ok + (size_t)g * (size_t)E;
+                      for (int32_t e = 0; e < E; e++)
+                          if (row[e])
+                              for (int32_t k = cl_off[(size_t)e]; k < cl_off[(size_t)e + 1]; k++) seen[(size_t)cl[(size_t)k]] = g;
+                  });
+    return CA_OK;
+}
+
+// Plan creation: the group records and streams, the facts of the lists (from the caller's
+// lists or from the option matrix), then the common tail: demand order, sort sharing,
+// buffers, fan map and uploads.  opt != NULL: group_off was derived from the matrix, pod_idx
+// is NULL and the lists are built on the device (k_option_lists).
 int plan_prepare(ca_estimate_plan* p, ca_mirror* m, const ca_podset* s, const int32_t* group_off,
-                 const int32_t* pod_idx, const ca_template* templates, int32_t G) {
+                 const int32_t* pod_idx, const OptionSrc* opt, const ca_template* templates, int32_t G) {
     p->m = m; p->s = s; p->G = G;
     {
         PlanStreams ps;                      // (pooled per device: plan_streams_acquire)
@@ -3083,109 +3419,21 @@ int plan_prepare(ca_estimate_plan* p, ca_mirror* m, const ca_podset* s, const in
     hipStream_t st = m->stream;
     int rc;
     const size_t tot = (size_t)std::max(p->total, 1);
-    // The sort classes first (sort_classes; CASIM_SORT_SHARE=0: one sort per group, for tests
-    // and A/B): groups with equal lists also share what the pass below finds, so it walks
-    // each class's first group only — a comparison of two lists costs far less per item than
-    // the walk's lookups.
-    std::vector<int32_t> sort_rep;
-    int32_t n_classes = G;
-    // (the list upload is queued by the caller's thread beside the comparisons, or beside the
-    // walk below when there are none)
-    hipError_t ce = hipSuccess;
-    rc = CA_OK;
-    bool uploaded = false;
-    auto upload = [&]() {
-        if ((rc = p->d_pod_idx.reserve(sizeof(int32_t) * tot)) == CA_OK && p->total)
-            ce = hipMemcpyAsync(p->d_pod_idx.ptr, pod_idx, sizeof(int32_t) * p->total, hipMemcpyHostToDevice, st);
-        uploaded = true;
-    };
-    if (p->bucket && s->cls_uniform && p->total > 0 &&
-        !(knob_env("CASIM_SORT_SHARE") && atoi(knob_env("CASIM_SORT_SHARE")) == 0))
-        n_classes = sort_classes(s, pod_idx, p->h_meta, templates, sort_rep, upload);
-    if (n_classes == G) sort_rep.clear();
-    // One pass over the lists (per-pod summaries of the podset: compact arrays instead of
-    // the 208-B records), split over host threads for big batches: index validation, the
-    // port / extended-resource flags and each group's summed requests for the demand
-    // order.  The lists travel to the device meanwhile (the caller's thread queues the copy);
-    // the item classes are gathered there from the podset's class column (k_item_cls).
-    {
-        // the groups walked and the prefix of their counts: the walk's items, split evenly
-        std::vector<int32_t> wg, woff(1, 0);
-        for (int32_t g = 0; g < G; g++)
-            if (sort_rep.empty() || sort_rep[g] == g) { wg.push_back(g); woff.push_back(woff.back() + p->h_meta[g].count); }
-        const int32_t K = (int32_t)wg.size(), wtotal = woff.back();
-        const int32_t T = std::max(1, std::min(7, wtotal / (1 << 17)));
-        struct Part { bool bad = false; uint8_t fl = 0; std::vector<double> c, mm; };
-        std::vector<Part> part((size_t)T);
-        const bool want_fl = s->any_ports || s->any_scalar;
-        auto work = [&](int32_t t) {
-            Part& pt = part[(size_t)t];
-            pt.c.assign((size_t)G, 0.0);
-            pt.mm.assign((size_t)G, 0.0);
-            const int32_t a = (int32_t)((int64_t)wtotal * t / T), b = (int32_t)((int64_t)wtotal * (t + 1) / T);
-            int32_t k0 = std::max(0, (int32_t)(std::upper_bound(woff.begin(), woff.end(), a) - woff.begin()) - 1);
-            const int32_t np_ = s->t.n_pods;
-            const int64_t* req = s->h_req.data();
-            for (int32_t v = a; v < b && !pt.bad;) {       // v: position in the walked groups' items
-                while (k0 < K - 1 && woff[(size_t)k0 + 1] <= v) k0++;
-                const int32_t g = wg[(size_t)k0];
-                const int32_t i = group_off[g] + (v - woff[(size_t)k0]);
-                const int32_t e = group_off[g] + (std::min(b, woff[(size_t)k0 + 1]) - woff[(size_t)k0]);
-                double c0 = 0, c1 = 0, m0 = 0, m1 = 0;   // (two chains each: the adds pipeline)
-                bool bad = false;
-                int32_t k = i;
-                for (; k + 1 < e; k += 2) {
-                    const int32_t p0 = pod_idx[k], p1 = pod_idx[k + 1];
-                    bad |= (uint32_t)p0 >= (uint32_t)np_ || (uint32_t)p1 >= (uint32_t)np_;
-                    if (bad) break;
-                    c0 += (double)req[2 * (size_t)p0]; m0 += (double)req[2 * (size_t)p0 + 1];
-                    c1 += (double)req[2 * (size_t)p1]; m1 += (double)req[2 * (size_t)p1 + 1];
-                }
-                if (!bad && k < e) {
-                    const int32_t p0 = pod_idx[k];
-                    bad = (uint32_t)p0 >= (uint32_t)np_;
-                    if (!bad) { c0 += (double)req[2 * (size_t)p0]; m0 += (double)req[2 * (size_t)p0 + 1]; }
-                }
-                if (bad) { pt.bad = true; break; }
-                if (want_fl)
-                    for (int32_t q = i; q < e; q++) pt.fl |= s->h_pflags[pod_idx[q]];
-                pt.c[(size_t)g] += c0 + c1;
-                pt.mm[(size_t)g] += m0 + m1;
-                v += e - i;
-            }
-        };
-        // task 0 (the caller's thread) queues the list upload if it is not queued yet,
-        // tasks 1..T walk the items
-        if (uploaded) casim::parallel_run(T, work);
-        else casim::parallel_run(T + 1, [&](int32_t t) { if (t > 0) work(t - 1); else upload(); });
-        if (rc != CA_OK) return rc;
-        CA_HIP_CHECK(ce);
-        bool bad = false;
-        p->demand.assign(G, 0.0);
-        std::vector<double> c((size_t)G, 0.0), mm((size_t)G, 0.0);
-        for (const Part& pt : part) {
-            bad |= pt.bad;
-            if (pt.fl & 1) p->use_ports = true;
-            if (pt.fl & 2) p->use_scalar = true;
-            for (int32_t g = 0; g < G; g++) { c[(size_t)g] += pt.c[(size_t)g]; mm[(size_t)g] += pt.mm[(size_t)g]; }
-        }
-        if (bad) {
-            CA_HIP_CHECK(hipStreamSynchronize(st));    // (the list copy may still read pod_idx)
-            return CA_EINVAL;
-        }
-        for (int32_t g = 0; g < G && !sort_rep.empty(); g++) {      // equal lists, equal sums
-            c[(size_t)g] = c[(size_t)sort_rep[g]];
-            mm[(size_t)g] = mm[(size_t)sort_rep[g]];
-        }
-        for (int32_t g = 0; g < G; g++) {
-            const GroupMeta& gm = p->h_meta[g];
-            double d = gm.tpods > 0 ? (double)gm.count / gm.tpods : 0.0;
-            if (gm.tcpu > 0) d = std::max(d, c[(size_t)g] / (double)gm.tcpu);
-            if (gm.tmem > 0) d = std::max(d, mm[(size_t)g] / (double)gm.tmem);
-            p->demand[g] = d;
-        }
+    ListFacts lf;
+    rc = opt ? lists_from_options(p, s, *opt, templates, G, lf)
+             : lists_from_host(p, s, group_off, pod_idx, templates, G, st, lf);
+    if (rc != CA_OK) return rc;
+    const std::vector<int32_t>& sort_rep = lf.sort_rep;
+    const int32_t n_classes = lf.n_classes;
+    p->demand.assign(G, 0.0);
+    for (int32_t g = 0; g < G; g++) {
+        const GroupMeta& gm = p->h_meta[g];
+        double d = gm.tpods > 0 ? (double)gm.count / gm.tpods : 0.0;
+        if (gm.tcpu > 0) d = std::max(d, lf.c[(size_t)g] / (double)gm.tcpu);
+        if (gm.tmem > 0) d = std::max(d, lf.mm[(size_t)g] / (double)gm.tmem);
+        p->demand[g] = d;
     }
-    p->decouple_ok = p->bucket && s->cls_uniform && groups_tie_free(s, pod_idx, p->h_meta, templates);
+    p->decouple_ok = lf.tie_free;
     // decoupled: one Go-order sort per sort class; the members read their representative's ids
     // and wait on its ready flag
     p->n_sorts = G;
@@ -3271,10 +3519,36 @@ int plan_prepare(ca_estimate_plan* p, ca_mirror* m, const ca_podset* s, const in
             return rc;
     }
     if (G) CA_HIP_CHECK(hipMemcpyAsync(p->d_meta.ptr, p->h_meta.data(), sizeof(GroupMeta) * G, hipMemcpyHostToDevice, st));
-    if (p->bucket && p->total > 0) {
-        // the lists as (pod, class) pairs: the class of every item next to its pod index, so
-        // the sorts and the run table read it in one coalesced load instead of two gathers
-        if ((rc = p->d_item_cls.reserve(sizeof(int32_t) * (size_t)p->total)) != CA_OK) return rc;
+    // the lists as (pod, class) pairs: the class of every item next to its pod index, so
+    // the sorts and the run table read it in one coalesced load instead of two gathers
+    if (p->bucket && p->total > 0 && (rc = p->d_item_cls.reserve(sizeof(int32_t) * (size_t)p->total)) != CA_OK) return rc;
+    DevBuf d_eg_off, d_eg_pod, d_ok, d_chunk_pre;      // option form: alive until the stream is drained below
+    if (opt) {
+        // the lists are built in HBM from the equivalence groups and the matrix: 4 B per
+        // pending pod and 1 B per pair go up instead of 4 B per item
+        if ((rc = p->d_pod_idx.reserve(sizeof(int32_t) * tot)) != CA_OK) return rc;
+        if (p->total > 0) {
+            const int32_t E = opt->n_eg, nch = (E + OPT_CHUNK - 1) / OPT_CHUNK;
+            const size_t n_egp = (size_t)opt->eg_off[E];
+            if ((rc = d_eg_off.reserve(sizeof(int32_t) * ((size_t)E + 1))) != CA_OK) return rc;
+            if ((rc = d_eg_pod.reserve(sizeof(int32_t) * n_egp)) != CA_OK) return rc;
+            if ((rc = d_ok.reserve((size_t)G * (size_t)E)) != CA_OK) return rc;
+            if ((rc = d_chunk_pre.reserve(sizeof(int32_t) * (size_t)G * (size_t)nch)) != CA_OK) return rc;
+            CA_HIP_CHECK(hipMemcpyAsync(d_eg_off.ptr, opt->eg_off, sizeof(int32_t) * ((size_t)E + 1), hipMemcpyHostToDevice, st));
+            CA_HIP_CHECK(hipMemcpyAsync(d_eg_pod.ptr, opt->eg_pod, sizeof(int32_t) * n_egp, hipMemcpyHostToDevice, st));
+            CA_HIP_CHECK(hipMemcpyAsync(d_ok.ptr, opt->ok, (size_t)G * (size_t)E, hipMemcpyHostToDevice, st));
+            hipLaunchKernelGGL(k_option_chunks, dim3(G), dim3(256), 0, st, d_eg_off.as<int32_t>(), d_ok.as<uint8_t>(), E, nch,
+                               d_chunk_pre.as<int32_t>());
+            CA_HIP_CHECK(hipGetLastError());
+            if (p->phase_events) CA_HIP_CHECK(hipEventRecord(p->ev[ca_estimate_plan::EV_START], st));
+            hipLaunchKernelGGL(k_option_lists, dim3((p->max_count + OPT_TILE - 1) / OPT_TILE, G), dim3(256), 0, st,
+                               p->d_meta.as<GroupMeta>(), d_eg_off.as<int32_t>(), d_eg_pod.as<int32_t>(), d_ok.as<uint8_t>(),
+                               E, nch, d_chunk_pre.as<int32_t>(), s->d_cls.as<int32_t>(), p->d_pod_idx.as<int32_t>(),
+                               p->bucket ? p->d_item_cls.as<int32_t>() : nullptr);
+            CA_HIP_CHECK(hipGetLastError());
+            if (p->phase_events) CA_HIP_CHECK(hipEventRecord(p->ev[ca_estimate_plan::EV_SCORE], st));
+        }
+    } else if (p->bucket && p->total > 0) {
         const int32_t nb = (int32_t)std::min<int64_t>(4096, (p->total + 255) / 256);
         hipLaunchKernelGGL(k_item_cls, dim3(nb), dim3(256), 0, st, p->d_pod_idx.as<int32_t>(),
                            s->d_cls.as<int32_t>(), p->d_item_cls.as<int32_t>(), p->total);
@@ -3282,6 +3556,8 @@ int plan_prepare(ca_estimate_plan* p, ca_mirror* m, const ca_podset* s, const in
     }
     if (G) CA_HIP_CHECK(hipMemcpyAsync(p->d_tmpl.ptr, templates, sizeof(ca_template) * G, hipMemcpyHostToDevice, st));
     CA_HIP_CHECK(hipStreamSynchronize(st));
+    if (opt && p->total > 0 && p->phase_events)
+        CA_HIP_CHECK(hipEventElapsedTime(&p->opt_lists_ms, p->ev[ca_estimate_plan::EV_START], p->ev[ca_estimate_plan::EV_SCORE]));
     return CA_OK;
 }
 
@@ -4133,9 +4409,53 @@ int ca_estimate_plan_create(ca_mirror* m, const ca_podset* s, const int32_t* gro
     if (!m || !s || !group_off || !out || n_groups < 0 || (n_groups > 0 && !templates)) return CA_EINVAL;
     CA_HIP_CHECK(hipSetDevice(m->device));
     ca_estimate_plan* p = new ca_estimate_plan();
-    int rc = plan_prepare(p, m, s, group_off, pod_idx, templates, n_groups);
+    int rc = plan_prepare(p, m, s, group_off, pod_idx, nullptr, templates, n_groups);
     if (rc != CA_OK) { delete p; return rc; }
     *out = p;
+    return CA_OK;
+}
+
+int ca_estimate_plan_create_options(ca_mirror* m, const ca_podset* s, const int32_t* eg_off, const int32_t* eg_pod,
+                                    int32_t n_eg, const uint8_t* ok, const ca_template* templates, int32_t n_groups,
+                                    int32_t* group_off_out, ca_estimate_plan** out) {
+    if (!m || !s || !eg_off || !out || !group_off_out || n_eg < 0 || n_groups < 0 || (n_groups > 0 && !templates) ||
+        (n_groups > 0 && n_eg > 0 && !ok))
+        return CA_EINVAL;
+    // every check before any launch or allocation
+    if (eg_off[0] != 0) return CA_EINVAL;
+    for (int32_t e = 0; e < n_eg; e++)
+        if (eg_off[e + 1] < eg_off[e]) return CA_EINVAL;
+    if (eg_off[n_eg] > 0 && !eg_pod) return CA_EINVAL;
+    const int32_t np_ = s->t.n_pods;
+    for (int32_t i = 0; i < eg_off[n_eg]; i++)
+        if ((uint32_t)eg_pod[i] >= (uint32_t)np_) return CA_EINVAL;
+    std::vector<int32_t> group_off((size_t)n_groups + 1, 0);
+    int64_t total = 0;
+    for (int32_t g = 0; g < n_groups; g++) {
+        const uint8_t* row = ok + (size_t)g * (size_t)n_eg;
+        int64_t c = 0;
+        for (int32_t e = 0; e < n_eg; e++) c += row[e] ? (int64_t)(eg_off[e + 1] - eg_off[e]) : 0;
+        total += c;
+        if (total > INT32_MAX) return CA_EINVAL;
+        group_off[(size_t)g + 1] = (int32_t)total;
+    }
+    CA_HIP_CHECK(hipSetDevice(m->device));
+    ca_estimate_plan* p = new ca_estimate_plan();
+    const OptionSrc opt{eg_off, eg_pod, n_eg, ok};
+    int rc = plan_prepare(p, m, s, group_off.data(), nullptr, &opt, templates, n_groups);
+    if (rc != CA_OK) { delete p; return rc; }
+    std::memcpy(group_off_out, group_off.data(), sizeof(int32_t) * group_off.size());
+    *out = p;
+    return CA_OK;
+}
+
+int ca_estimate_plan_fetch_lists(const ca_estimate_plan* p, int32_t* pod_idx, int32_t* item_cls) {
+    if (!p) return CA_EINVAL;
+    CA_HIP_CHECK(hipSetDevice(p->m->device));
+    if (p->total > 0 && pod_idx)
+        CA_HIP_CHECK(hipMemcpy(pod_idx, p->d_pod_idx.ptr, sizeof(int32_t) * (size_t)p->total, hipMemcpyDeviceToHost));
+    if (p->total > 0 && item_cls && p->bucket)
+        CA_HIP_CHECK(hipMemcpy(item_cls, p->d_item_cls.ptr, sizeof(int32_t) * (size_t)p->total, hipMemcpyDeviceToHost));
     return CA_OK;
 }
 
@@ -4182,8 +4502,9 @@ int ca_estimate_plan_stats(const ca_estimate_plan* p, int32_t* rounds, float* ch
 
 int ca_estimate_plan_timings(const ca_estimate_plan* p, float* out, int32_t cap) {
     if (!p || (cap > 0 && !out)) return CA_EINVAL;
-    const int32_t n = 12;
+    const int32_t n = 13;
     for (int32_t i = 0; i < 7 && i < cap; i++) out[i] = p->t_ms[i];
+    if (cap > 12) out[12] = p->opt_lists_ms;
     if (cap > 7) out[7] = (float)p->pub_state;
     if (cap > 8) out[8] = (float)p->ran_decoupled;
     if (cap > 9) out[9] = (float)p->ran_table_chain;

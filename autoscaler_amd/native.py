@@ -91,6 +91,8 @@ def load() -> C.CDLL:
         "ca_expansion_plan_kernel_ms": ([vp, p(C.c_float)], C.c_int),
         "ca_estimate_batch": ([vp, vp, vp, vp, vp, i32, vp, p(i32), vp, vp, vp], C.c_int),
         "ca_estimate_plan_create": ([vp, vp, vp, vp, vp, i32, p(vp)], C.c_int),
+        "ca_estimate_plan_create_options": ([vp, vp, vp, vp, i32, vp, vp, i32, vp, p(vp)], C.c_int),
+        "ca_estimate_plan_fetch_lists": ([vp, vp, vp], C.c_int),
         "ca_estimate_plan_run": ([vp, vp, p(i32), vp, vp, vp], C.c_int),
         "ca_estimate_plan_run_u16": ([vp, vp, p(i32), vp, vp], C.c_int),
         "ca_estimate_plan_destroy": ([vp], C.c_int),
@@ -217,6 +219,7 @@ def exported_symbols() -> list[str]:
         "ca_mirror_node_pods", "ca_podset_create", "ca_podset_destroy", "ca_fits_any_node", "ca_check_predicates",
         "ca_fits_matrix", "ca_check_templates", "ca_expansion_plan_create", "ca_expansion_plan_run",
         "ca_expansion_plan_destroy", "ca_expansion_plan_kernel_ms", "ca_estimate_batch", "ca_estimate_plan_create", "ca_estimate_plan_run",
+        "ca_estimate_plan_create_options", "ca_estimate_plan_fetch_lists",
         "ca_estimate_plan_run_u16",
         "ca_estimate_plan_destroy", "ca_estimate_plan_stats", "ca_estimate_plan_chain_info", "ca_estimate_plan_rebase",
         "ca_estimate_plan_timings",
@@ -554,6 +557,15 @@ class Mirror:
         with EstimatePlan(self, table, group_off, pod_idx, templates, podset=podset) as plan:
             return plan.run(max_nodes, last_index, want_nodes=want_nodes)
 
+    def estimate_options(self, table_or_podset, eg_off, eg_pod, ok, templates: np.ndarray, max_nodes: int,
+                         last_index: int = 0, want_nodes: bool = True) -> tuple:
+        """Mirror.estimate on the options' lists built in device memory from the pod
+        equivalence groups and the verdict matrix (EstimatePlan.from_options): plan, one run,
+        teardown.  Returns (EstimateOutput, group_off): group g's results lie at
+        sched_pod[group_off[g]:group_off[g + 1]]."""
+        with EstimatePlan.from_options(self, table_or_podset, eg_off, eg_pod, ok, templates) as plan:
+            return plan.run(max_nodes, last_index, want_nodes=want_nodes), plan.group_off
+
     def check_templates(self, table: abi.PodTable, samples, templates: np.ndarray, podset=None,
                         verdict_only: bool = False, out=None) -> np.ndarray:
         """ComputeExpansionOption's feasibility (orchestrator.go:455-481) for every (node
@@ -877,22 +889,65 @@ class EstimatePlan:
         self.pod_idx = np.ascontiguousarray(pod_idx, dtype=np.int32)
         self.templates = np.ascontiguousarray(templates, dtype=abi.TEMPLATE_DTYPE)
         self.G = len(self.templates)
-        self.total = int(self.group_off[-1]) if len(self.group_off) else 0
+        s = self._podset_handle(mirror, table, podset)
+        p = C.c_void_p()
+        st = self.lib.ca_estimate_plan_create(mirror.h, s, ptr(self.group_off), ptr(self.pod_idx),
+                                              ptr(self.templates), self.G, C.byref(p))
+        self._created(st, p, "ca_estimate_plan_create")
+
+    @classmethod
+    def from_options(cls, mirror: Mirror, table_or_podset, eg_off, eg_pod, ok, templates: np.ndarray) -> "EstimatePlan":
+        """The plan of ComputeExpansionOption's lists (orchestrator.go:468-482) without the lists
+        (ca_estimate_plan_create_options): the pods of pod equivalence group e are
+        eg_pod[eg_off[e]:eg_off[e + 1]] (indices into the pod table), `ok` is the [G][E] verdict
+        matrix (nonzero = the group's sample passed, Mirror.check_templates(verdict_only=True) or
+        ``feas["type"] == CA_PRED_OK``), and group g's list is the concatenation of the passing
+        groups' pods in group order.  The lists are built in device memory; `.group_off` comes
+        from the library and `.pod_idx` is None (fetch_lists() copies the lists out).
+        `table_or_podset`: an abi.PodTable (uploaded here) or a resident PodSet."""
+        self = cls.__new__(cls)
+        self.m = mirror
+        self.lib = mirror.lib
+        self.templates = np.ascontiguousarray(templates, dtype=abi.TEMPLATE_DTYPE)
+        self.G = len(self.templates)
+        self.pod_idx = None
+        ego = np.ascontiguousarray(eg_off, dtype=np.int32)
+        egp = np.ascontiguousarray(eg_pod, dtype=np.int32)
+        if ego.ndim != 1 or len(ego) < 1:
+            raise ValueError("eg_off: n_eg + 1 offsets")
+        n_eg = len(ego) - 1
+        if len(egp) < int(ego[-1]):
+            raise ValueError("eg_pod is shorter than eg_off[-1]")
+        okm = np.ascontiguousarray(ok)
+        if okm.dtype != np.uint8:
+            okm = np.ascontiguousarray(okm != 0, dtype=np.uint8)
+        if okm.size != self.G * n_eg:
+            raise ValueError("ok: one verdict per (node group, pod equivalence group)")
+        self.group_off = np.zeros(self.G + 1, np.int32)
+        is_set = isinstance(table_or_podset, PodSet)
+        s = self._podset_handle(mirror, None if is_set else table_or_podset, table_or_podset if is_set else None)
+        p = C.c_void_p()
+        st = self.lib.ca_estimate_plan_create_options(mirror.h, s, ptr(ego), ptr(egp), n_eg, ptr(okm),
+                                                      ptr(self.templates), self.G, ptr(self.group_off), C.byref(p))
+        self._created(st, p, "ca_estimate_plan_create_options")
+        return self
+
+    def _podset_handle(self, mirror: Mirror, table, podset):
         if podset is None:
             s = C.c_void_p()
             _check(self.lib.ca_podset_create(mirror.h, table.ref, C.byref(s)), "ca_podset_create")
             self.podset = s
-        else:
-            self.podset = None
-            s = podset.h
-        p = C.c_void_p()
-        st = self.lib.ca_estimate_plan_create(mirror.h, s, ptr(self.group_off), ptr(self.pod_idx),
-                                              ptr(self.templates), self.G, C.byref(p))
+            return s
+        self.podset = None
+        return podset.h
+
+    def _created(self, st: int, p, what: str) -> None:
         if st != abi.CA_OK:
             if self.podset:
                 self.lib.ca_podset_destroy(self.podset)
-            raise CasimError(st, "ca_estimate_plan_create")
+            raise CasimError(st, what)
         self.h = p
+        self.total = int(self.group_off[-1]) if len(self.group_off) else 0
         n = max(self.total, 1)
         self._pinned = PinnedArray(self.lib, 2 * n, np.int32)     # sched_pod | sched_node
         self.sched_pod = self._pinned.array[:n]
@@ -944,6 +999,15 @@ class EstimatePlan:
         out = np.full(max(self.total, 1), -1, np.int32)
         _check(self.lib.ca_estimate_plan_fetch(self.h, ptr(out)), "ca_estimate_plan_fetch")
         return out[: self.total]
+
+    def fetch_lists(self) -> tuple:
+        """The plan's device lists (ca_estimate_plan_fetch_lists): (pod_idx [total], the score
+        class of every item [total], or None off the bucket path)."""
+        pod_idx = np.full(max(self.total, 1), -1, np.int32)
+        item_cls = np.full(max(self.total, 1), -1, np.int32)
+        _check(self.lib.ca_estimate_plan_fetch_lists(self.h, ptr(pod_idx), ptr(item_cls)), "ca_estimate_plan_fetch_lists")
+        has_cls = self.total == 0 or bool((item_cls[: self.total] >= 0).all())
+        return pod_idx[: self.total], (item_cls[: self.total] if has_cls else None)
 
     def option_sums(self) -> tuple:
         """resourcesForPods (waste.go:74-87) of every group of the last run, summed on the
@@ -1015,15 +1079,15 @@ class EstimatePlan:
         self.lib.ca_estimate_plan_stats(self.h, C.byref(r), C.byref(a), C.byref(b), C.byref(c))
         sens, succ = C.c_int32(0), C.c_int32(0)
         self.lib.ca_estimate_plan_chain_info(self.h, C.byref(sens), C.byref(succ))
-        t = (C.c_float * 12)()
-        self.lib.ca_estimate_plan_timings(self.h, t, 12)
+        t = (C.c_float * 13)()
+        self.lib.ca_estimate_plan_timings(self.h, t, 13)
         names = ("score_ms", "merge_ms", "emit_ms", "chain_ms", "compact_ms", "d2h_ms", "host_ms")
         return {"rounds": r.value, "chain_ms": a.value, "sort_ms": b.value, "total_ms": c.value,
                 "lin_sensitive": sens.value, "had_success": succ.value,
                 "phases": {k: float(v) for k, v in zip(names, t)},
                 "results_path": ("copied", "published", "publisher_gave_up")[int(t[7])],
                 "decoupled": bool(t[8]), "table_chain": bool(t[9]), "sorts": int(t[10]),
-                "sort_parts": int(t[11])}
+                "sort_parts": int(t[11]), "option_lists_ms": float(t[12])}
 
     def set_phase_timing(self, on: bool) -> None:
         """Per-phase timing events on later runs (on by default; off keeps them off the

@@ -264,12 +264,14 @@ class UtilInput:
             self.nodes, self.off, self.pods, _ = _util_rows(w, placed_node, zeros)
 
 
-def run(backend, util_fn, w: RunOnceWorkload, timers=None, row_zeros=_zeros, expand_fn=None) -> RunOnceResult:
+def run(backend, util_fn, w: RunOnceWorkload, timers=None, row_zeros=_zeros, expand_fn=None,
+        option_lists: str = "device") -> RunOnceResult:
     """One loop on `backend` (native.Mirror or pyoracle.OracleState, freshly loaded with
     W.load_filter) with `util_fn(UtilInput, now_ns) -> UTIL_INFO rows` (its attribute `want`,
     default "full", picks the input form); `row_zeros` allocates full utilization rows;
     `expand_fn(backend, podset, samples, templates)` (e.g. DeviceExpansion) replaces the
-    backend's check_templates for step 2."""
+    backend's check_templates for step 2.  `option_lists="host"` keeps step 3's pod lists on
+    the host for a backend that could build them itself (A/B, scripts/cold_options.py)."""
     f = w.filt
     r = RunOnceResult()
     clock = time.perf_counter
@@ -297,16 +299,27 @@ def run(backend, util_fn, w: RunOnceWorkload, timers=None, row_zeros=_zeros, exp
     # a [G][E] uint8 verdict (1 = fits, the device's verdict-only form) or ca_pred_result rows
     r.options = res.astype(np.uint8) if res.dtype == np.uint8 else (res["type"] == 0).astype(np.uint8)
 
-    # 3. Estimate of every option, one batch
-    off, idx = [0], []
-    for g in range(len(w.templates)):
-        for e in np.nonzero(r.options[g])[0]:
-            idx.extend(groups[e])
-        off.append(len(idx))
-    group_off = np.array(off, np.int32)
-    pod_idx = np.array(idx, np.int32)
-    t = clock()
-    est = backend.estimate(f.pending, group_off, pod_idx, w.templates, MAX_NODES, r.last_index, **kw)
+    # 3. Estimate of every option, one batch.  A backend with estimate_options (the device
+    # mirror) gets the equivalence groups and the verdict matrix and builds the options' pod
+    # lists in its own memory; the others (the oracle, a sharded rank) get the lists.
+    # (looked up on the class: a wrapper that forwards unknown attributes does not count)
+    if option_lists == "device" and callable(getattr(type(backend), "estimate_options", None)):
+        eg_off = np.zeros(len(groups) + 1, np.int32)
+        np.cumsum([len(g) for g in groups], out=eg_off[1:])
+        eg_pod = np.fromiter((i for g in groups for i in g), np.int32, int(eg_off[-1]))
+        t = clock()
+        est, group_off = backend.estimate_options(ps if ps is not None else f.pending, eg_off, eg_pod, r.options,
+                                                  w.templates, MAX_NODES, r.last_index)
+    else:
+        off, idx = [0], []
+        for g in range(len(w.templates)):
+            for e in np.nonzero(r.options[g])[0]:
+                idx.extend(groups[e])
+            off.append(len(idx))
+        group_off = np.array(off, np.int32)
+        pod_idx = np.array(idx, np.int32)
+        t = clock()
+        est = backend.estimate(f.pending, group_off, pod_idx, w.templates, MAX_NODES, r.last_index, **kw)
     r.ms["estimate"] = (clock() - t) * 1e3
     r.est_results, r.est_sched = est.results.copy(), est.sched_pod.copy()
     r.last_index = int(est.last_index)                 # one PredicateChecker for the whole loop

@@ -119,14 +119,16 @@ def ComputeExpansionOptions(snapshot: ClusterSnapshot, checker: SchedulerBasedPr
 @contextmanager
 def _resident_estimate(snapshot: ClusterSnapshot, checker: SchedulerBasedPredicateChecker,
                        limiter: ThresholdBasedEstimationLimiter, node_groups: list, est_groups: list,
-                       est_index: list, all_pods: list, pod_idx, offs, multi):
+                       est_index: list, all_pods: list, pod_idx, offs, multi, options=None):
     """What ComputeBestExpansionOption and ComputeBalancedScaleUp share after the feasibility
     matrix: the Estimate plan over `all_pods` (group g's pods are pod_idx[offs[g]:offs[g + 1]]),
     one run with the lists left in device memory, the checker's counters, the :174 filter and the
     device form of the options.  The plan is an EstimatePlan on the snapshot's backend, or, with
     `multi` (a native.Multi), a MultiEstimatePlan over its mirrors, each of which is first made to
     hold the snapshot (ClusterSnapshot.sync_replica).  Yields (plan, run output, valid group
-    indices, DeviceOptions, node infos by node group id); the plan is closed on exit."""
+    indices, DeviceOptions, node infos by node group id); the plan is closed on exit.  With
+    `options` = (eg_off, eg_pod, ok) (see _option_inputs) the plan builds the lists itself
+    (native.EstimatePlan.from_options) and pod_idx / offs are not read."""
     from . import native
     from .expander import DeviceOptions, resources_for_node
     from .predicatechecker import unsupported
@@ -138,7 +140,9 @@ def _resident_estimate(snapshot: ClusterSnapshot, checker: SchedulerBasedPredica
         templates[g] = snapshot.interner.encode_template(info.node, list(info.pods))
     caps = [resources_for_node(info.node) for _, info in est_groups]
     with unsupported("Estimate: the snapshot holds a pod with required anti-affinity"):
-        if multi is None:
+        if options is not None:
+            plan = native.EstimatePlan.from_options(snapshot.backend, table, *options, templates)
+        elif multi is None:
             plan = native.EstimatePlan(snapshot.backend, table, np.array(offs, np.int32),
                                        np.array(pod_idx, np.int32), templates)
         else:
@@ -163,6 +167,33 @@ def _resident_estimate(snapshot: ClusterSnapshot, checker: SchedulerBasedPredica
         yield plan, out, valid, dev, node_infos
 
 
+# "device": at C2 the option-form constructor's median (0.378 ms) lies below the host-list
+# constructor's lower quartile (0.710 ms), DESIGN.md §5 "Cold latency" / profiles/option_lists_cold.txt
+OPTION_LISTS_DEFAULT = "device"
+
+
+def _option_inputs(pod_groups: list, est_index: list, feas):
+    """The device form of the options' lists (native.EstimatePlan.from_options): the shared pod
+    table holds every pod of a pod group that passes anywhere once, group after group (so a pod
+    has one id in every option); the pod groups are its CSR; `ok` is the feasibility matrix of
+    the node groups that got pods over those pod groups.  Returns (all_pods, (eg_off, eg_pod, ok))."""
+    ok = (feas["type"] == abi.CA_PRED_OK)[np.asarray(est_index, np.int64)]
+    passing = np.nonzero(ok.any(axis=0))[0]
+    all_pods, eg_off = [], [0]
+    for e in passing:
+        all_pods.extend(pod_groups[e].pods)
+        eg_off.append(len(all_pods))
+    ok = np.ascontiguousarray(ok[:, passing], np.uint8)
+    return all_pods, (np.array(eg_off, np.int32), np.arange(len(all_pods), dtype=np.int32), ok)
+
+
+def _check_option_lists(option_lists) -> str:
+    option_lists = OPTION_LISTS_DEFAULT if option_lists is None else option_lists
+    if option_lists not in ("device", "host"):
+        raise ValueError('option_lists: "device" or "host"')
+    return option_lists
+
+
 def _backend_must_be_mirror(snapshot: ClusterSnapshot, who: str) -> None:
     from . import native
     if not isinstance(snapshot.backend, native.Mirror):
@@ -172,7 +203,7 @@ def _backend_must_be_mirror(snapshot: ClusterSnapshot, who: str) -> None:
 
 def ComputeBestExpansionOption(snapshot: ClusterSnapshot, checker: SchedulerBasedPredicateChecker,  # noqa: N802
                                pod_groups: list, node_groups: list, limiter: ThresholdBasedEstimationLimiter,
-                               strategy, multi=None):
+                               strategy, multi=None, option_lists=None):
     """ComputeExpansionOptions followed by the orchestrator's option filter and
     ExpanderStrategy.BestOption (orchestrator.go:139-195), with the options' pod lists left
     in device memory: one Estimate plan run with device results, the `len(Pods) > 0 &&
@@ -182,17 +213,26 @@ def ComputeBestExpansionOption(snapshot: ClusterSnapshot, checker: SchedulerBase
     ExpansionOption or None, the feasibility matrix); the snapshot's backend must be the
     device mirror.  `multi` (a native.Multi): the Estimate plan is sharded over its mirrors,
     which are synced to the snapshot first; the feasibility matrix still runs on the backend and
-    everything after the run is the same code."""
+    everything after the run is the same code.  `option_lists`: "host" appends the options' pod
+    lists here and uploads them; "device" encodes every pod of a passing pod group once and
+    hands the pod groups and the feasibility matrix to the plan, which builds the lists in
+    device memory (same results).  With `multi` the host lists stay: the sharded plan takes
+    lists only."""
     _backend_must_be_mirror(snapshot, "ComputeBestExpansionOption")
+    option_lists = _check_option_lists(option_lists)
     est_groups, est_index, feas = _feasible_pods(snapshot, pod_groups, node_groups)
     if not est_groups:
         return None, feas
-    all_pods, offs = [], [0]
-    for pods, _ in est_groups:
-        all_pods.extend(pods)
-        offs.append(len(all_pods))
+    all_pods, offs, options = [], [0], None
+    if option_lists == "device" and multi is None:
+        all_pods, options = _option_inputs(pod_groups, est_index, feas)
+    else:
+        for pods, _ in est_groups:
+            all_pods.extend(pods)
+            offs.append(len(all_pods))
     with _resident_estimate(snapshot, checker, limiter, node_groups, est_groups, est_index, all_pods,
-                            np.arange(len(all_pods), dtype=np.int32), offs, multi) as (plan, out, valid, dev, node_infos):
+                            np.arange(len(all_pods), dtype=np.int32), offs, multi,
+                            options) as (plan, out, valid, dev, node_infos):
         if not valid:                      # "No expansion options" (orchestrator.go:181-188)
             return None, feas
         options = []
@@ -207,7 +247,7 @@ def ComputeBestExpansionOption(snapshot: ClusterSnapshot, checker: SchedulerBase
 
 def ComputeBalancedScaleUp(snapshot: ClusterSnapshot, checker: SchedulerBasedPredicateChecker,  # noqa: N802
                            pod_groups: list, node_groups: list, limiter: ThresholdBasedEstimationLimiter,
-                           strategy, processor, cap_new_nodes=None, multi=None):
+                           strategy, processor, cap_new_nodes=None, multi=None, option_lists=None):
     """ScaleUp from the options to the final scale-up plan (orchestrator.go:139-313) with
     --balance-similar-node-groups, the options' pod lists left in device memory: the
     feasibility matrix; ONE Estimate plan over a shared pod table (every pending pod encoded
@@ -222,24 +262,31 @@ def ComputeBalancedScaleUp(snapshot: ClusterSnapshot, checker: SchedulerBasedPre
     list.  The node groups are objects with Id() / TargetSize() / MaxSize().  Returns (the best
     ExpansionOption or None, [ScaleUpInfo], the feasibility matrix).  `multi`: as on
     ComputeBestExpansionOption; the winner's list then crosses devices only if a similar group's
-    option lies in another block (casim.h, ca_multi_estimate_plan_groups_missing_pods)."""
+    option lies in another block (casim.h, ca_multi_estimate_plan_groups_missing_pods).
+    `option_lists`: as on ComputeBestExpansionOption ("device": the pod_idx slices are built in
+    device memory from the pod groups and the feasibility matrix; with `multi` the host lists
+    stay, the sharded plan takes lists only)."""
     from .nodegroupset import filter_plan_groups_by_pods
 
     _backend_must_be_mirror(snapshot, "ComputeBalancedScaleUp")
+    option_lists = _check_option_lists(option_lists)
     est_groups, est_index, feas = _feasible_pods(snapshot, pod_groups, node_groups)
     if not est_groups:
         return None, [], feas
     all_pods, row = [], {}
-    pod_idx, offs = [], [0]
-    for pods, _ in est_groups:                  # the shared table: every feasible pod once
-        for p in pods:
-            if id(p) not in row:
-                row[id(p)] = len(all_pods)
-                all_pods.append(p)
-            pod_idx.append(row[id(p)])
-        offs.append(len(pod_idx))
+    pod_idx, offs, options = [], [0], None
+    if option_lists == "device" and multi is None:
+        all_pods, options = _option_inputs(pod_groups, est_index, feas)
+    else:
+        for pods, _ in est_groups:                  # the shared table: every feasible pod once
+            for p in pods:
+                if id(p) not in row:
+                    row[id(p)] = len(all_pods)
+                    all_pods.append(p)
+                pod_idx.append(row[id(p)])
+            offs.append(len(pod_idx))
     with _resident_estimate(snapshot, checker, limiter, node_groups, est_groups, est_index, all_pods, pod_idx, offs,
-                            multi) as (plan, out, valid, dev, node_infos):
+                            multi, options) as (plan, out, valid, dev, node_infos):
         if not valid:                      # "No expansion options" (orchestrator.go:181-188)
             return None, [], feas
         group_of = {node_groups[est_index[g]][0].Id(): g for g in valid}      # expansionOptions' keys

@@ -418,6 +418,24 @@ typedef struct ca_estimate_plan ca_estimate_plan;
 int ca_estimate_plan_create(ca_mirror* m, const ca_podset* s, const int32_t* group_off,
                             const int32_t* pod_idx, const ca_template* templates,
                             int32_t n_groups, ca_estimate_plan** out);
+/* The same plan from the inputs of ComputeExpansionOption's append (orchestrator.go:468-482)
+ * instead of its output: the pods of equivalence group e are eg_pod[eg_off[e] .. eg_off[e+1])
+ * (pod-set indices, the reference's order), ok is [n_groups][n_eg] in the layout of
+ * ca_check_templates' out_ok, and group g's list is the concatenation, for e ascending with
+ * ok[g*n_eg+e] != 0, of group e's pods.  The lists are built in device memory: eg_off, eg_pod
+ * and ok are all that is uploaded.  The plan is the one ca_estimate_plan_create builds from
+ * those lists; group_off_out (n_groups + 1) receives their offsets, which index results /
+ * sched_pod.  A row with no passing group is an empty group.  CA_EINVAL, before any launch or
+ * allocation: eg_off[0] != 0 or eg_off decreasing, an eg_pod entry outside the pod set, a
+ * total item count that does not fit int32. */
+int ca_estimate_plan_create_options(ca_mirror* m, const ca_podset* s,
+                                    const int32_t* eg_off, const int32_t* eg_pod, int32_t n_eg,
+                                    const uint8_t* ok, const ca_template* templates, int32_t n_groups,
+                                    int32_t* group_off_out, ca_estimate_plan** out);
+/* The plan's device lists copied out (plans of either constructor; for tests and Go-side
+ * checks): pod_idx[total] and the score class of every item, item_cls[total].  Either may be
+ * NULL.  item_cls exists on the bucket path only; otherwise it is left untouched. */
+int ca_estimate_plan_fetch_lists(const ca_estimate_plan* p, int32_t* pod_idx, int32_t* item_cls);
 int ca_estimate_plan_run(ca_estimate_plan* p, const ca_limiter* limiter, int32_t* last_index,
                          ca_estimate_result* results, int32_t* sched_pod, int32_t* sched_node);
 /* sched_pod == NULL (and sched_node == NULL) in ca_estimate_plan_run keeps the scheduled
@@ -451,7 +469,10 @@ int ca_estimate_plan_stats(const ca_estimate_plan* p, int32_t* rounds, float* ch
  * path (CASIM_SORT_SHARE=0: one per group), otherwise the number of groups; [11] the
  * parts those sorts' ids were finished and flagged in: a long list's sort fans out over
  * several workgroups of a second launch (CASIM_SORT_FAN=0: never), every other sort is one
- * part, so [11] == [10] when nothing fanned.  Writes min(cap, 12) values; returns 12. */
+ * part, so [11] == [10] when nothing fanned; [12] not of the last run but of the plan's
+ * creation: the device time of the kernel that built the lists from the option matrix
+ * (ca_estimate_plan_create_options), 0 for a plan created from host lists.  Writes
+ * min(cap, 13) values; returns 13. */
 int ca_estimate_plan_timings(const ca_estimate_plan* p, float* out, int32_t cap);
 /* Record the per-phase timing events of later runs (on: default) or not: 8 event records
  * per run on the host's launch path; with them off, ca_estimate_plan_timings[0..5] and the
