@@ -22,6 +22,9 @@ CA_EXPANDER_MOST_PODS, CA_EXPANDER_LEAST_WASTE = 1, 2     # ca_expander_best_opt
 # workgroup, and pod equivalence groups per partial sum (tests place their cases at both)
 OPTION_LIST_TILE, OPTION_LIST_CHUNK = 2048, 256
 
+# podgroups.hip PG_TILE: positions of the pending list per workgroup pass of ca_pod_groups_create
+POD_GROUP_TILE = 2048
+
 CA_MAX_SCALAR = 8
 CA_LABEL_WORDS = 4
 CA_PORT_WORDS = 2

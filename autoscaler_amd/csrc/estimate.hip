@@ -3133,6 +3133,10 @@ struct OptionSrc {
     const int32_t* eg_pod;
     int32_t n_eg;
     const uint8_t* ok;
+    // a ca_pod_groups handle's copies in device memory (ca_estimate_plan_create_groups): the
+    // two arrays are read where they lie instead of being uploaded; NULL otherwise
+    const int32_t* d_eg_off = nullptr;
+    const int32_t* d_eg_pod = nullptr;
 };
 
 // shared sorts are looked for (CASIM_SORT_SHARE=0: one sort per group, for tests and A/B)
@@ -3530,19 +3534,25 @@ int plan_prepare(ca_estimate_plan* p, ca_mirror* m, const ca_podset* s, const in
         if (p->total > 0) {
             const int32_t E = opt->n_eg, nch = (E + OPT_CHUNK - 1) / OPT_CHUNK;
             const size_t n_egp = (size_t)opt->eg_off[E];
-            if ((rc = d_eg_off.reserve(sizeof(int32_t) * ((size_t)E + 1))) != CA_OK) return rc;
-            if ((rc = d_eg_pod.reserve(sizeof(int32_t) * n_egp)) != CA_OK) return rc;
+            const int32_t* eg_off_d = opt->d_eg_off;
+            const int32_t* eg_pod_d = opt->d_eg_pod;
+            if (!eg_off_d) {
+                if ((rc = d_eg_off.reserve(sizeof(int32_t) * ((size_t)E + 1))) != CA_OK) return rc;
+                if ((rc = d_eg_pod.reserve(sizeof(int32_t) * n_egp)) != CA_OK) return rc;
+                CA_HIP_CHECK(hipMemcpyAsync(d_eg_off.ptr, opt->eg_off, sizeof(int32_t) * ((size_t)E + 1), hipMemcpyHostToDevice, st));
+                CA_HIP_CHECK(hipMemcpyAsync(d_eg_pod.ptr, opt->eg_pod, sizeof(int32_t) * n_egp, hipMemcpyHostToDevice, st));
+                eg_off_d = d_eg_off.as<int32_t>();
+                eg_pod_d = d_eg_pod.as<int32_t>();
+            }
             if ((rc = d_ok.reserve((size_t)G * (size_t)E)) != CA_OK) return rc;
             if ((rc = d_chunk_pre.reserve(sizeof(int32_t) * (size_t)G * (size_t)nch)) != CA_OK) return rc;
-            CA_HIP_CHECK(hipMemcpyAsync(d_eg_off.ptr, opt->eg_off, sizeof(int32_t) * ((size_t)E + 1), hipMemcpyHostToDevice, st));
-            CA_HIP_CHECK(hipMemcpyAsync(d_eg_pod.ptr, opt->eg_pod, sizeof(int32_t) * n_egp, hipMemcpyHostToDevice, st));
             CA_HIP_CHECK(hipMemcpyAsync(d_ok.ptr, opt->ok, (size_t)G * (size_t)E, hipMemcpyHostToDevice, st));
-            hipLaunchKernelGGL(k_option_chunks, dim3(G), dim3(256), 0, st, d_eg_off.as<int32_t>(), d_ok.as<uint8_t>(), E, nch,
+            hipLaunchKernelGGL(k_option_chunks, dim3(G), dim3(256), 0, st, eg_off_d, d_ok.as<uint8_t>(), E, nch,
                                d_chunk_pre.as<int32_t>());
             CA_HIP_CHECK(hipGetLastError());
             if (p->phase_events) CA_HIP_CHECK(hipEventRecord(p->ev[ca_estimate_plan::EV_START], st));
             hipLaunchKernelGGL(k_option_lists, dim3((p->max_count + OPT_TILE - 1) / OPT_TILE, G), dim3(256), 0, st,
-                               p->d_meta.as<GroupMeta>(), d_eg_off.as<int32_t>(), d_eg_pod.as<int32_t>(), d_ok.as<uint8_t>(),
+                               p->d_meta.as<GroupMeta>(), eg_off_d, eg_pod_d, d_ok.as<uint8_t>(),
                                E, nch, d_chunk_pre.as<int32_t>(), s->d_cls.as<int32_t>(), p->d_pod_idx.as<int32_t>(),
                                p->bucket ? p->d_item_cls.as<int32_t>() : nullptr);
             CA_HIP_CHECK(hipGetLastError());
@@ -4442,6 +4452,37 @@ int ca_estimate_plan_create_options(ca_mirror* m, const ca_podset* s, const int3
     CA_HIP_CHECK(hipSetDevice(m->device));
     ca_estimate_plan* p = new ca_estimate_plan();
     const OptionSrc opt{eg_off, eg_pod, n_eg, ok};
+    int rc = plan_prepare(p, m, s, group_off.data(), nullptr, &opt, templates, n_groups);
+    if (rc != CA_OK) { delete p; return rc; }
+    std::memcpy(group_off_out, group_off.data(), sizeof(int32_t) * group_off.size());
+    *out = p;
+    return CA_OK;
+}
+
+int ca_estimate_plan_create_groups(ca_mirror* m, const ca_podset* s, const ca_pod_groups* g, const uint8_t* ok,
+                                   const ca_template* templates, int32_t n_groups, int32_t* group_off_out,
+                                   ca_estimate_plan** out) {
+    if (!m || !s || !g || g->m != m || g->s != s || !out || !group_off_out || n_groups < 0 ||
+        (n_groups > 0 && !templates) || (n_groups > 0 && g->n_eg > 0 && !ok))
+        return CA_EINVAL;
+    // the handle's CSR was built from checked indices: only the rows' totals are taken here
+    const int32_t n_eg = g->n_eg;
+    const int32_t* eg_off = g->h_eg_off.data();
+    std::vector<int32_t> group_off((size_t)n_groups + 1, 0);
+    int64_t total = 0;
+    for (int32_t q = 0; q < n_groups; q++) {
+        const uint8_t* row = ok + (size_t)q * (size_t)n_eg;
+        int64_t c = 0;
+        for (int32_t e = 0; e < n_eg; e++) c += row[e] ? (int64_t)(eg_off[e + 1] - eg_off[e]) : 0;
+        total += c;
+        if (total > INT32_MAX) return CA_EINVAL;
+        group_off[(size_t)q + 1] = (int32_t)total;
+    }
+    CA_HIP_CHECK(hipSetDevice(m->device));
+    ca_estimate_plan* p = new ca_estimate_plan();
+    OptionSrc opt{eg_off, g->h_eg_pod.data(), n_eg, ok};
+    opt.d_eg_off = g->d_eg_off;
+    opt.d_eg_pod = g->d_eg_pod;
     int rc = plan_prepare(p, m, s, group_off.data(), nullptr, &opt, templates, n_groups);
     if (rc != CA_OK) { delete p; return rc; }
     std::memcpy(group_off_out, group_off.data(), sizeof(int32_t) * group_off.size());

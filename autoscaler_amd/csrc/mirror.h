@@ -351,6 +351,33 @@ struct ca_podset {
     // — provided no two classes of a group tie on their float64 score against the group's
     // template (checked per plan: ca_estimate_plan::decouple_ok)
     bool cls_uniform = false;
+    // BuildPodGroups' view of the records (podgroups.hip): per pod its similar class, or -1 for
+    // a pod that is always a group of its own (no controller, DaemonSet); n_sim = max + 1
+    std::vector<int32_t> h_sim;
+    int32_t n_sim = 0;
+};
+
+// Pod equivalence groups built on the device (podgroups.hip): a CSR over the unschedulable
+// pods of a pod set, resident for ca_expansion_plan_run_groups (the samples) and
+// ca_estimate_plan_create_groups (the lists' source), with a host copy for fetch and for the
+// plan's per-group facts.
+struct ca_pod_groups {
+    ca_mirror* m = nullptr;
+    const ca_podset* s = nullptr;
+    int32_t device = 0;                    // m->device (destroy does not touch the mirror)
+    int32_t n_eg = 0, n_pods = 0;
+    casim::DevBuf d_out;                   // eg_off | samples | eg_pod
+    int32_t* d_eg_off = nullptr;           // [n_eg + 1]
+    int32_t* d_samples = nullptr;          // [n_eg]: eg_pod[eg_off[e]]
+    int32_t* d_eg_pod = nullptr;           // [n_pods]
+    std::vector<int32_t> h_eg_off, h_eg_pod;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    float build_ms = 0.f;                  // device time of the build (events around its launches)
+    int32_t launches = 0;
+    ~ca_pod_groups() {
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+    }
 };
 
 namespace casim {

@@ -1473,8 +1473,13 @@ int ca_podset_create(ca_mirror* m, const ca_pod_table* t, ca_podset** out) {
     s->n_host = t->n_pods;
     s->h_req.resize(2 * (size_t)t->n_pods);
     s->h_pflags.assign((size_t)t->n_pods, 0);
+    s->h_sim.assign((size_t)t->n_pods, -1);
     for (int32_t i = 0; i < t->n_pods; i++) {
         const ca_pod_spec& ps = t->pods[i];
+        if (ps.similar_class >= 0 && !(ps.flags & CA_POD_DAEMONSET)) {
+            s->h_sim[i] = ps.similar_class;
+            s->n_sim = std::max(s->n_sim, ps.similar_class + 1);
+        }
         s->any_oos |= (ps.flags & CA_POD_OUT_OF_SCOPE) != 0;
         s->any_refs |= ps.aff_term_count > 0 || ((ps.flags & CA_POD_PREFILTER_NAMES) && ps.prefilter_count > 0);
         s->h_req[2 * (size_t)i] = ps.req_milli_cpu;
@@ -1846,15 +1851,22 @@ int ca_expansion_plan_create(ca_mirror* m, const ca_template* templates, int32_t
     return CA_OK;
 }
 
-int ca_expansion_plan_run(ca_expansion_plan* p, const ca_podset* s, const int32_t* samples, int32_t n_samples,
-                          ca_pred_result* out, uint8_t* out_ok) {
+// ca_expansion_plan_run and ca_expansion_plan_run_groups: the samples come from the caller
+// (checked and copied into the plan's page-locked buffer) or lie in device memory already
+// (d_samples != NULL: a ca_pod_groups handle's, built from checked indices)
+static int expansion_plan_run(ca_expansion_plan* p, const ca_podset* s, const int32_t* samples,
+                              const int32_t* d_samples, int32_t n_samples, ca_pred_result* out, uint8_t* out_ok) {
     if (!p || !s || s->m != p->m || n_samples < 0) return CA_EINVAL;
     if (n_samples == 0 || p->G == 0) return CA_OK;
-    if (!samples || (!out && !out_ok)) return CA_EINVAL;
+    if ((!samples && !d_samples) || (!out && !out_ok)) return CA_EINVAL;
     const auto t_entry = std::chrono::steady_clock::now();
     ca_mirror* m = p->m;
     int rc;
-    if ((rc = check_samples(m, s, samples, n_samples)) != CA_OK) return rc;
+    if (d_samples) {
+        if (m->n_scope_blockers > 0) return CA_EUNSUPPORTED;
+    } else if ((rc = check_samples(m, s, samples, n_samples)) != CA_OK) {
+        return rc;
+    }
     CA_HIP_CHECK(hipSetDevice(m->device));
     const size_t pairs = (size_t)p->G * (size_t)n_samples;
     const size_t nsm = (sizeof(int32_t) * (size_t)n_samples + 63) & ~(size_t)63;
@@ -1864,7 +1876,7 @@ int ca_expansion_plan_run(ca_expansion_plan* p, const ca_podset* s, const int32_
     // the samples are read and the results written in page-locked memory through its
     // device mapping: no copy-engine round trips for a call of a few kilobytes
     char* hio = p->io.as<char>();
-    std::memcpy(hio, samples, sizeof(int32_t) * (size_t)n_samples);
+    if (!d_samples) std::memcpy(hio, samples, sizeof(int32_t) * (size_t)n_samples);
     if (p->io_host != p->io.ptr) {
         void* dio_v = nullptr;
         CA_HIP_CHECK(hipHostGetDevicePointer(&dio_v, p->io.ptr, 0));
@@ -1893,7 +1905,7 @@ int ca_expansion_plan_run(ca_expansion_plan* p, const ca_podset* s, const int32_
                        reinterpret_cast<const NodeHot*>(rows),
                        reinterpret_cast<const NodeExt*>(rows + sizeof(NodeHot) * G),
                        reinterpret_cast<const NodeStatic*>(rows + (sizeof(NodeHot) + sizeof(NodeExt)) * G),
-                       reinterpret_cast<const int32_t*>(dio), n_samples, s->t.hot.as<PodHot>(),
+                       d_samples ? d_samples : reinterpret_cast<const int32_t*>(dio), n_samples, s->t.hot.as<PodHot>(),
                        s->t.spec.as<ca_pod_spec>(), s->t.terms.as<ca_selector_term>(), s->t.reqs.as<ca_selector_req>(),
                        out ? reinterpret_cast<ca_pred_result*>(d_out ? d_out : dio + nsm) : nullptr,
                        out_ok ? reinterpret_cast<uint8_t*>(d_ok ? d_ok : dio + nsm + no) : nullptr);
@@ -1912,6 +1924,17 @@ int ca_expansion_plan_run(ca_expansion_plan* p, const ca_podset* s, const int32_
     if (out && !d_out) std::memcpy(out, hio + nsm, sizeof(ca_pred_result) * pairs);
     if (out_ok && !d_ok) std::memcpy(out_ok, hio + nsm + no, pairs);
     return CA_OK;
+}
+
+int ca_expansion_plan_run(ca_expansion_plan* p, const ca_podset* s, const int32_t* samples, int32_t n_samples,
+                          ca_pred_result* out, uint8_t* out_ok) {
+    return expansion_plan_run(p, s, samples, nullptr, n_samples, out, out_ok);
+}
+
+int ca_expansion_plan_run_groups(ca_expansion_plan* p, const ca_podset* s, const ca_pod_groups* g,
+                                 ca_pred_result* out, uint8_t* out_ok) {
+    if (!p || !s || !g || g->s != s || g->m != p->m) return CA_EINVAL;
+    return expansion_plan_run(p, s, nullptr, g->d_samples, g->n_eg, out, out_ok);
 }
 
 int ca_expansion_plan_kernel_ms(const ca_expansion_plan* p, float* kernel_ms) {

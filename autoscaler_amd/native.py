@@ -93,6 +93,13 @@ def load() -> C.CDLL:
         "ca_estimate_plan_create": ([vp, vp, vp, vp, vp, i32, p(vp)], C.c_int),
         "ca_estimate_plan_create_options": ([vp, vp, vp, vp, i32, vp, vp, i32, vp, p(vp)], C.c_int),
         "ca_estimate_plan_fetch_lists": ([vp, vp, vp], C.c_int),
+        "ca_pod_groups_create": ([vp, vp, vp, i32, vp, vp, i32, p(vp)], C.c_int),
+        "ca_pod_groups_info": ([vp, p(i32), p(i32)], C.c_int),
+        "ca_pod_groups_fetch": ([vp, vp, vp], C.c_int),
+        "ca_pod_groups_timings": ([vp, p(C.c_float), i32], C.c_int),
+        "ca_pod_groups_destroy": ([vp], C.c_int),
+        "ca_expansion_plan_run_groups": ([vp, vp, vp, vp, vp], C.c_int),
+        "ca_estimate_plan_create_groups": ([vp, vp, vp, vp, vp, i32, vp, p(vp)], C.c_int),
         "ca_estimate_plan_run": ([vp, vp, p(i32), vp, vp, vp], C.c_int),
         "ca_estimate_plan_run_u16": ([vp, vp, p(i32), vp, vp], C.c_int),
         "ca_estimate_plan_destroy": ([vp], C.c_int),
@@ -220,6 +227,8 @@ def exported_symbols() -> list[str]:
         "ca_fits_matrix", "ca_check_templates", "ca_expansion_plan_create", "ca_expansion_plan_run",
         "ca_expansion_plan_destroy", "ca_expansion_plan_kernel_ms", "ca_estimate_batch", "ca_estimate_plan_create", "ca_estimate_plan_run",
         "ca_estimate_plan_create_options", "ca_estimate_plan_fetch_lists",
+        "ca_pod_groups_create", "ca_pod_groups_info", "ca_pod_groups_fetch", "ca_pod_groups_timings",
+        "ca_pod_groups_destroy", "ca_expansion_plan_run_groups", "ca_estimate_plan_create_groups",
         "ca_estimate_plan_run_u16",
         "ca_estimate_plan_destroy", "ca_estimate_plan_stats", "ca_estimate_plan_chain_info", "ca_estimate_plan_rebase",
         "ca_estimate_plan_timings",
@@ -558,13 +567,26 @@ class Mirror:
             return plan.run(max_nodes, last_index, want_nodes=want_nodes)
 
     def estimate_options(self, table_or_podset, eg_off, eg_pod, ok, templates: np.ndarray, max_nodes: int,
-                         last_index: int = 0, want_nodes: bool = True) -> tuple:
+                         last_index: int = 0, want_nodes: bool = True, groups=None) -> tuple:
         """Mirror.estimate on the options' lists built in device memory from the pod
         equivalence groups and the verdict matrix (EstimatePlan.from_options): plan, one run,
         teardown.  Returns (EstimateOutput, group_off): group g's results lie at
-        sched_pod[group_off[g]:group_off[g + 1]]."""
-        with EstimatePlan.from_options(self, table_or_podset, eg_off, eg_pod, ok, templates) as plan:
+        sched_pod[group_off[g]:group_off[g + 1]].  `groups` (a PodGroups built on the same
+        resident PodSet): the equivalence groups are read from the handle's device memory
+        (EstimatePlan.from_groups) and eg_off / eg_pod are not read."""
+        if groups is not None:
+            plan = EstimatePlan.from_groups(self, table_or_podset, groups, ok, templates)
+        else:
+            plan = EstimatePlan.from_options(self, table_or_podset, eg_off, eg_pod, ok, templates)
+        with plan:
             return plan.run(max_nodes, last_index, want_nodes=want_nodes), plan.group_off
+
+    def build_pod_groups(self, podset: "PodSet", order=None, node=None, class_owner=None) -> "PodGroups":
+        """equivalence.BuildPodGroups on the device (ca_pod_groups_create): the pods
+        order[k] of `podset` (None: table order) with node[k] < 0 (None: all of them), grouped
+        by similar class with at most 10 groups per controller (class_owner[c]: the controller
+        of class c, Interner.class_owners; None: no cap)."""
+        return PodGroups(self, podset, order, node, class_owner)
 
     def check_templates(self, table: abi.PodTable, samples, templates: np.ndarray, podset=None,
                         verdict_only: bool = False, out=None) -> np.ndarray:
@@ -877,6 +899,69 @@ class PodSet:
         self.close()
 
 
+class PodGroups:
+    """``ca_pod_groups``: the pod equivalence groups of a resident PodSet's unschedulable pods,
+    built and kept in device memory (include/casim.h; equivalence/groups.go:38-102).  A CSR:
+    group e's pods are eg_pod[eg_off[e]:eg_off[e + 1]] (pod-set indices), its sample the first
+    of them.  Feeds ExpansionPlan.run(groups=) and EstimatePlan.from_groups."""
+
+    def __init__(self, mirror: "Mirror", podset: "PodSet", order=None, node=None, class_owner=None):
+        self.lib = mirror.lib
+        self.mirror = mirror
+        self.podset = podset
+        self.h = None
+        od = None if order is None else np.ascontiguousarray(order, dtype=np.int32)
+        nd = None if node is None else np.ascontiguousarray(node, dtype=np.int32)
+        n = len(od) if od is not None else (len(nd) if nd is not None else len(podset.table))
+        if nd is not None and len(nd) != n:
+            raise ValueError("node: one entry per listed pod")
+        co = None if class_owner is None else np.ascontiguousarray(class_owner, dtype=np.int32)
+        h = C.c_void_p()
+        _check(self.lib.ca_pod_groups_create(mirror.h, podset.h, ptr(od) if od is not None else None, n,
+                                             ptr(nd) if nd is not None else None,
+                                             ptr(co) if co is not None else None, len(co) if co is not None else 0,
+                                             C.byref(h)), "ca_pod_groups_create")
+        self.h = h
+        a, b = C.c_int32(0), C.c_int32(0)
+        _check(self.lib.ca_pod_groups_info(self.h, C.byref(a), C.byref(b)), "ca_pod_groups_info")
+        self.n_groups, self.n_pods = a.value, b.value
+
+    def fetch(self) -> tuple:
+        """(eg_off [n_groups + 1], eg_pod [n_pods]) int32."""
+        eg_off = np.zeros(self.n_groups + 1, np.int32)
+        eg_pod = np.zeros(self.n_pods, np.int32)
+        _check(self.lib.ca_pod_groups_fetch(self.h, ptr(eg_off), ptr(eg_pod) if self.n_pods else None),
+               "ca_pod_groups_fetch")
+        return eg_off, eg_pod
+
+    def samples(self) -> np.ndarray:
+        """The first pod of every group."""
+        eg_off, eg_pod = self.fetch()
+        return eg_pod[eg_off[:-1]] if self.n_groups else np.zeros(0, np.int32)
+
+    def timings(self) -> dict:
+        t = (C.c_float * 2)()
+        self.lib.ca_pod_groups_timings(self.h, t, 2)
+        return {"build_ms": float(t[0]), "launches": int(t[1])}
+
+    def close(self) -> None:
+        if self.h:
+            self.lib.ca_pod_groups_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class EstimatePlan:
     """``ca_estimate_plan``: device-resident groups for repeated Estimate batches."""
 
@@ -930,6 +1015,33 @@ class EstimatePlan:
         st = self.lib.ca_estimate_plan_create_options(mirror.h, s, ptr(ego), ptr(egp), n_eg, ptr(okm),
                                                       ptr(self.templates), self.G, ptr(self.group_off), C.byref(p))
         self._created(st, p, "ca_estimate_plan_create_options")
+        return self
+
+    @classmethod
+    def from_groups(cls, mirror: Mirror, podset: "PodSet", groups: "PodGroups", ok, templates: np.ndarray) -> "EstimatePlan":
+        """from_options with the pod equivalence groups taken from a PodGroups handle built on
+        `podset` (ca_estimate_plan_create_groups): the CSR is read where it lies in device
+        memory; only `ok` ([G][groups.n_groups]) is uploaded.  The same plan as from_options on
+        groups.fetch()."""
+        self = cls.__new__(cls)
+        self.m = mirror
+        self.lib = mirror.lib
+        self.templates = np.ascontiguousarray(templates, dtype=abi.TEMPLATE_DTYPE)
+        self.G = len(self.templates)
+        self.pod_idx = None
+        if not isinstance(podset, PodSet) or groups.podset is not podset:
+            raise ValueError("from_groups: the PodSet the groups were built on")
+        okm = np.ascontiguousarray(ok)
+        if okm.dtype != np.uint8:
+            okm = np.ascontiguousarray(okm != 0, dtype=np.uint8)
+        if okm.size != self.G * groups.n_groups:
+            raise ValueError("ok: one verdict per (node group, pod equivalence group)")
+        self.group_off = np.zeros(self.G + 1, np.int32)
+        s = self._podset_handle(mirror, None, podset)
+        p = C.c_void_p()
+        st = self.lib.ca_estimate_plan_create_groups(mirror.h, s, groups.h, ptr(okm), ptr(self.templates), self.G,
+                                                     ptr(self.group_off), C.byref(p))
+        self._created(st, p, "ca_estimate_plan_create_groups")
         return self
 
     def _podset_handle(self, mirror: Mirror, table, podset):
@@ -1149,11 +1261,22 @@ class ExpansionPlan:
                "ca_expansion_plan_create")
         self.h = h
 
-    def run(self, podset: "PodSet", samples, verdict_only: bool = False, out=None) -> np.ndarray:
+    def run(self, podset: "PodSet", samples=None, verdict_only: bool = False, out=None, groups=None) -> np.ndarray:
         """[G][E] ca_pred_result (or with verdict_only a [G][E] uint8, 1 = fits), as
-        Mirror.check_templates returns it."""
-        sm = np.ascontiguousarray(samples, dtype=np.int32)
+        Mirror.check_templates returns it.  `groups` (a PodGroups built on `podset`): the samples
+        are the groups' first pods, read from the handle's device memory
+        (ca_expansion_plan_run_groups); `samples` is not read."""
         G = len(self.templates)
+        if groups is not None:
+            if out is None:
+                out = np.zeros((G, groups.n_groups), np.uint8 if verdict_only else abi.PRED_RESULT_DTYPE)
+            full, ok = (None, out) if verdict_only else (out, None)
+            _check(self.lib.ca_expansion_plan_run_groups(self.h, podset.h, groups.h,
+                                                         ptr(full) if full is not None else None,
+                                                         ptr(ok) if ok is not None else None),
+                   "ca_expansion_plan_run_groups")
+            return out
+        sm = np.ascontiguousarray(samples, dtype=np.int32)
         if out is None:
             out = np.zeros((G, len(sm)), np.uint8 if verdict_only else abi.PRED_RESULT_DTYPE)
         full, ok = (None, out) if verdict_only else (out, None)

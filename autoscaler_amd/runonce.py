@@ -171,7 +171,8 @@ class DeviceExpansion:
         self.tbytes = None
         self.rows = None
 
-    def __call__(self, backend, podset, samples: np.ndarray, templates: np.ndarray) -> np.ndarray:
+    def __call__(self, backend, podset, samples, templates: np.ndarray, groups=None) -> np.ndarray:
+        """`groups` (a native.PodGroups on `podset`): the samples are read from the handle."""
         from . import native
         # the resident rows are re-uploaded when the node groups change: a new array, or the
         # same array updated in place (ADVICE r5: keyed on the content, not only the identity)
@@ -185,8 +186,9 @@ class DeviceExpansion:
             self.rows = self.rows or native.PinnedRows()
         # the loop needs only the option set: one verdict byte per (group, sample) crosses PCIe
         # instead of a 16-byte ca_pred_result
-        out = self.rows.zeros("ok", len(templates) * len(samples), np.uint8, zero=False)
-        return self.plan.run(podset, samples, verdict_only=True, out=out.reshape(len(templates), len(samples)))
+        n_s = groups.n_groups if groups is not None else len(samples)
+        out = self.rows.zeros("ok", len(templates) * n_s, np.uint8, zero=False)
+        return self.plan.run(podset, samples, verdict_only=True, out=out.reshape(len(templates), n_s), groups=groups)
 
     def close(self):
         if self.plan is not None:
@@ -265,13 +267,22 @@ class UtilInput:
 
 
 def run(backend, util_fn, w: RunOnceWorkload, timers=None, row_zeros=_zeros, expand_fn=None,
-        option_lists: str = "device") -> RunOnceResult:
+        option_lists: str = "device", pod_groups: str = "host") -> RunOnceResult:
     """One loop on `backend` (native.Mirror or pyoracle.OracleState, freshly loaded with
     W.load_filter) with `util_fn(UtilInput, now_ns) -> UTIL_INFO rows` (its attribute `want`,
     default "full", picks the input form); `row_zeros` allocates full utilization rows;
     `expand_fn(backend, podset, samples, templates)` (e.g. DeviceExpansion) replaces the
     backend's check_templates for step 2.  `option_lists="host"` keeps step 3's pod lists on
-    the host for a backend that could build them itself (A/B, scripts/cold_options.py)."""
+    the host for a backend that could build them itself (A/B, scripts/cold_options.py).
+    `pod_groups="device"` (the device mirror only): the pod equivalence groups between steps 1
+    and 2 are built in device memory from the filter's verdicts (native.Mirror.build_pod_groups,
+    without the cap of 10 groups per controller, as _equivalence_groups), and steps 2 and 3 read
+    them there (`expand_fn` is then called with samples None and `groups=` the handle); "host"
+    groups the unschedulable pods in the Python loop.  The device form puts a
+    DaemonSet pod in a group of its own (groups.go:68-72), which _equivalence_groups does not: the
+    two agree on a workload whose unschedulable pods carry no CA_POD_DAEMONSET."""
+    if pod_groups not in ("host", "device"):
+        raise ValueError('pod_groups: "host" or "device"')
     f = w.filt
     r = RunOnceResult()
     clock = time.perf_counter
@@ -288,13 +299,28 @@ def run(backend, util_fn, w: RunOnceWorkload, timers=None, row_zeros=_zeros, exp
     unsched = f.order[fo.node < 0]
 
     # 2. expansion options: CheckPredicates of every equivalence group's sample on every template
-    groups = _equivalence_groups(f.pending.pods, unsched)
-    samples = np.array([g[0] for g in groups], np.int32)
-    t = clock()
-    if expand_fn is not None and ps is not None:
-        res = expand_fn(backend, ps, samples, w.templates)
+    pg = None
+    if pod_groups == "device":
+        if ps is None or not callable(getattr(type(backend), "build_pod_groups", None)):
+            raise TypeError('pod_groups="device" needs the device mirror as backend')
+        pg = backend.build_pod_groups(ps, order=f.order, node=fo.node, class_owner=None)
+        n_eg = pg.n_groups
+        t = clock()
+        if expand_fn is not None:
+            res = expand_fn(backend, ps, None, w.templates, groups=pg)
+        else:
+            from . import native
+            with native.ExpansionPlan(backend, w.templates) as ep:
+                res = ep.run(ps, verdict_only=True, groups=pg)
     else:
-        res = backend.check_templates(f.pending, samples, w.templates, **kw)
+        groups = _equivalence_groups(f.pending.pods, unsched)
+        n_eg = len(groups)
+        samples = np.array([g[0] for g in groups], np.int32)
+        t = clock()
+        if expand_fn is not None and ps is not None:
+            res = expand_fn(backend, ps, samples, w.templates)
+        else:
+            res = backend.check_templates(f.pending, samples, w.templates, **kw)
     r.ms["expansion"] = (clock() - t) * 1e3
     # a [G][E] uint8 verdict (1 = fits, the device's verdict-only form) or ca_pred_result rows
     r.options = res.astype(np.uint8) if res.dtype == np.uint8 else (res["type"] == 0).astype(np.uint8)
@@ -303,7 +329,12 @@ def run(backend, util_fn, w: RunOnceWorkload, timers=None, row_zeros=_zeros, exp
     # mirror) gets the equivalence groups and the verdict matrix and builds the options' pod
     # lists in its own memory; the others (the oracle, a sharded rank) get the lists.
     # (looked up on the class: a wrapper that forwards unknown attributes does not count)
-    if option_lists == "device" and callable(getattr(type(backend), "estimate_options", None)):
+    if pg is not None:
+        t = clock()
+        est, group_off = backend.estimate_options(ps, None, None, r.options, w.templates, MAX_NODES, r.last_index,
+                                                  groups=pg)
+        pg.close()
+    elif option_lists == "device" and callable(getattr(type(backend), "estimate_options", None)):
         eg_off = np.zeros(len(groups) + 1, np.int32)
         np.cumsum([len(g) for g in groups], out=eg_off[1:])
         eg_pod = np.fromiter((i for g in groups for i in g), np.int32, int(eg_off[-1]))
@@ -362,7 +393,7 @@ def run(backend, util_fn, w: RunOnceWorkload, timers=None, row_zeros=_zeros, exp
     r.last_index = int(sw.last_index)
     r.ms["total"] = sum(r.ms.values())
     r.sizes = {"pending": int(len(f.order)), "placed_by_filter": int(placed.size), "unschedulable": int(len(unsched)),
-               "equivalence_groups": len(groups), "options_pairs": int(r.options.size),
+               "equivalence_groups": n_eg, "options_pairs": int(r.options.size),
                "estimate_items": int(group_off[-1]), "scale_down_candidates": int(len(low)),
                "empty": int(len(r.empty)), "sweep_candidates": int(len(cand)), "pods_to_move": int(len(move_pods)),
                "removable": int(r.sweep_results["removable"].sum())}

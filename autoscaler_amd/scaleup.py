@@ -17,6 +17,10 @@ groups that passed, template).  Here:
 Order: the reference ranges over BuildPodGroups' map (random order in Go); groups
 here are in first-occurrence order, so an option's pods are in a canonical order
 (Estimate's tie order).
+
+The grouping can also be built on the device: ``BuildPodGroupsOnDevice`` returns the same
+groups from the interned records (``ca_pod_groups_create``) and carries the resident handle,
+which ``ComputeBestExpansionOption`` and ``ComputeBalancedScaleUp`` read in place.
 """
 from __future__ import annotations
 
@@ -62,6 +66,73 @@ def BuildPodGroups(pods: list) -> list:  # noqa: N802
             egs.append((sig, len(groups)))
         groups.append(PodGroup([pod]))
     return groups
+
+
+class DevicePodGroups(list):
+    """BuildPodGroupsOnDevice's result: the list[PodGroup] of BuildPodGroups(pods), plus the
+    groups where they were built: `pods` (the input, whose positions are the pod-set indices),
+    `table` / `podset` (their records, resident on the snapshot's backend) and `handle` (the
+    native.PodGroups over them).  close() frees the device side; the list stays usable."""
+
+    pods: list
+    table = None
+    podset = None
+    handle = None
+
+    def _build(self, snapshot: ClusterSnapshot, table) -> None:
+        self.close()
+        self.table = table
+        self.podset = snapshot.backend.podset(table)
+        cls = table.pods["similar_class"]
+        n_classes = int(cls.max()) + 1 if len(cls) else 0
+        self.handle = snapshot.backend.build_pod_groups(
+            self.podset, class_owner=snapshot.interner.class_owners(max(n_classes, 0)))
+
+    def resident(self, snapshot: ClusterSnapshot, table):
+        """(podset, handle) for `table`, the current encoding of `pods`: rebuilt when the
+        interner's universes grew since the build and the records changed."""
+        same = self.handle is not None and all(
+            getattr(self.table, k).tobytes() == getattr(table, k).tobytes() for k in ("pods", "terms", "reqs", "names"))
+        if not same:
+            self._build(snapshot, table)
+        return self.podset, self.handle
+
+    def close(self) -> None:
+        if self.handle is not None:
+            self.handle.close()
+            self.handle = None
+        if self.podset is not None:
+            self.podset.close()
+            self.podset = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def BuildPodGroupsOnDevice(snapshot: ClusterSnapshot, pods: list) -> DevicePodGroups:  # noqa: N802
+    """BuildPodGroups(pods) computed on the snapshot's device mirror from the interned records
+    (similar class, DaemonSet flag, the classes' controllers; ca_pod_groups_create): the same
+    groups with the same pods in the same order.  The returned list carries the resident handle
+    (DevicePodGroups); close() it, or use it as a context manager."""
+    _backend_must_be_mirror(snapshot, "BuildPodGroupsOnDevice")
+    pods = list(pods)
+    snapshot.ensure(pods=pods)
+    out = DevicePodGroups()
+    out.pods = pods
+    out._build(snapshot, snapshot.interner.encode_pods(pods))
+    eg_off, eg_pod = out.handle.fetch()
+    for e in range(out.handle.n_groups):
+        out.append(PodGroup([pods[i] for i in eg_pod[eg_off[e]:eg_off[e + 1]]]))
+    return out
+
+
+def _device_groups(pod_groups, option_lists: str, multi):
+    """The DevicePodGroups whose handle the facades read: given as the pod groups, with the
+    lists built on the device and one mirror."""
+    return pod_groups if isinstance(pod_groups, DevicePodGroups) and option_lists == "device" and multi is None else None
 
 
 @dataclass
@@ -119,7 +190,7 @@ def ComputeExpansionOptions(snapshot: ClusterSnapshot, checker: SchedulerBasedPr
 @contextmanager
 def _resident_estimate(snapshot: ClusterSnapshot, checker: SchedulerBasedPredicateChecker,
                        limiter: ThresholdBasedEstimationLimiter, node_groups: list, est_groups: list,
-                       est_index: list, all_pods: list, pod_idx, offs, multi, options=None):
+                       est_index: list, all_pods: list, pod_idx, offs, multi, options=None, device_groups=None):
     """What ComputeBestExpansionOption and ComputeBalancedScaleUp share after the feasibility
     matrix: the Estimate plan over `all_pods` (group g's pods are pod_idx[offs[g]:offs[g + 1]]),
     one run with the lists left in device memory, the checker's counters, the :174 filter and the
@@ -128,7 +199,9 @@ def _resident_estimate(snapshot: ClusterSnapshot, checker: SchedulerBasedPredica
     hold the snapshot (ClusterSnapshot.sync_replica).  Yields (plan, run output, valid group
     indices, DeviceOptions, node infos by node group id); the plan is closed on exit.  With
     `options` = (eg_off, eg_pod, ok) (see _option_inputs) the plan builds the lists itself
-    (native.EstimatePlan.from_options) and pod_idx / offs are not read."""
+    (native.EstimatePlan.from_options) and pod_idx / offs are not read.  With `device_groups` (a
+    DevicePodGroups; all_pods is then its pods in input order and options[2] the matrix over all
+    of its groups) the plan reads the groups from the handle (native.EstimatePlan.from_groups)."""
     from . import native
     from .expander import DeviceOptions, resources_for_node
     from .predicatechecker import unsupported
@@ -140,7 +213,10 @@ def _resident_estimate(snapshot: ClusterSnapshot, checker: SchedulerBasedPredica
         templates[g] = snapshot.interner.encode_template(info.node, list(info.pods))
     caps = [resources_for_node(info.node) for _, info in est_groups]
     with unsupported("Estimate: the snapshot holds a pod with required anti-affinity"):
-        if options is not None:
+        if device_groups is not None:
+            ps, handle = device_groups.resident(snapshot, table)
+            plan = native.EstimatePlan.from_groups(snapshot.backend, ps, handle, options[2], templates)
+        elif options is not None:
             plan = native.EstimatePlan.from_options(snapshot.backend, table, *options, templates)
         elif multi is None:
             plan = native.EstimatePlan(snapshot.backend, table, np.array(offs, np.int32),
@@ -187,6 +263,14 @@ def _option_inputs(pod_groups: list, est_index: list, feas):
     return all_pods, (np.array(eg_off, np.int32), np.arange(len(all_pods), dtype=np.int32), ok)
 
 
+def _handle_inputs(dpg: DevicePodGroups, est_index: list, feas):
+    """_option_inputs for pod groups built on the device: the pod table is the given pods in
+    input order (the handle's indices), the CSR stays in the handle, and `ok` covers every pod
+    group: a group that passes nowhere is an all-zero column.  Returns (all_pods, (None, None, ok))."""
+    ok = (feas["type"] == abi.CA_PRED_OK)[np.asarray(est_index, np.int64)]
+    return dpg.pods, (None, None, np.ascontiguousarray(ok, np.uint8))
+
+
 def _check_option_lists(option_lists) -> str:
     option_lists = OPTION_LISTS_DEFAULT if option_lists is None else option_lists
     if option_lists not in ("device", "host"):
@@ -224,7 +308,10 @@ def ComputeBestExpansionOption(snapshot: ClusterSnapshot, checker: SchedulerBase
     if not est_groups:
         return None, feas
     all_pods, offs, options = [], [0], None
-    if option_lists == "device" and multi is None:
+    dpg = _device_groups(pod_groups, option_lists, multi)
+    if dpg is not None:
+        all_pods, options = _handle_inputs(dpg, est_index, feas)
+    elif option_lists == "device" and multi is None:
         all_pods, options = _option_inputs(pod_groups, est_index, feas)
     else:
         for pods, _ in est_groups:
@@ -232,7 +319,7 @@ def ComputeBestExpansionOption(snapshot: ClusterSnapshot, checker: SchedulerBase
             offs.append(len(all_pods))
     with _resident_estimate(snapshot, checker, limiter, node_groups, est_groups, est_index, all_pods,
                             np.arange(len(all_pods), dtype=np.int32), offs, multi,
-                            options) as (plan, out, valid, dev, node_infos):
+                            options, dpg) as (plan, out, valid, dev, node_infos):
         if not valid:                      # "No expansion options" (orchestrator.go:181-188)
             return None, feas
         options = []
@@ -275,7 +362,10 @@ def ComputeBalancedScaleUp(snapshot: ClusterSnapshot, checker: SchedulerBasedPre
         return None, [], feas
     all_pods, row = [], {}
     pod_idx, offs, options = [], [0], None
-    if option_lists == "device" and multi is None:
+    dpg = _device_groups(pod_groups, option_lists, multi)
+    if dpg is not None:
+        all_pods, options = _handle_inputs(dpg, est_index, feas)
+    elif option_lists == "device" and multi is None:
         all_pods, options = _option_inputs(pod_groups, est_index, feas)
     else:
         for pods, _ in est_groups:                  # the shared table: every feasible pod once
@@ -286,7 +376,7 @@ def ComputeBalancedScaleUp(snapshot: ClusterSnapshot, checker: SchedulerBasedPre
                 pod_idx.append(row[id(p)])
             offs.append(len(pod_idx))
     with _resident_estimate(snapshot, checker, limiter, node_groups, est_groups, est_index, all_pods, pod_idx, offs,
-                            multi, options) as (plan, out, valid, dev, node_infos):
+                            multi, options, dpg) as (plan, out, valid, dev, node_infos):
         if not valid:                      # "No expansion options" (orchestrator.go:181-188)
             return None, [], feas
         group_of = {node_groups[est_index[g]][0].Id(): g for g in valid}      # expansionOptions' keys
@@ -308,5 +398,5 @@ def ComputeBalancedScaleUp(snapshot: ClusterSnapshot, checker: SchedulerBasedPre
     return best, processor.BalanceScaleUpBetweenGroups([best.node_group] + kept, new_nodes), feas
 
 
-__all__ = ["PodGroup", "BuildPodGroups", "ExpansionOption", "ComputeExpansionOptions", "ComputeBestExpansionOption",
+__all__ = ["PodGroup", "BuildPodGroups", "BuildPodGroupsOnDevice", "DevicePodGroups","ExpansionOption", "ComputeExpansionOptions", "ComputeBestExpansionOption",
            "ComputeBalancedScaleUp", "NodeInfo", "Pod"]

@@ -436,6 +436,49 @@ int ca_estimate_plan_create_options(ca_mirror* m, const ca_podset* s,
  * checks): pod_idx[total] and the score class of every item, item_cls[total].  Either may be
  * NULL.  item_cls exists on the bucket path only; otherwise it is left untouched. */
 int ca_estimate_plan_fetch_lists(const ca_estimate_plan* p, int32_t* pod_idx, int32_t* item_cls);
+
+/* Pod equivalence groups built in device memory (equivalence.BuildPodGroups,
+ * core/scaleup/equivalence/groups.go:38-102), the input of the two calls above and of
+ * ca_expansion_plan_run.  The list is the pods order[0..n) of the pod set (order NULL: pods
+ * 0..n-1 in table order) without those with node[k] >= 0 (FilterOutSchedulable's out_node; NULL:
+ * every pod is in the list).  The rule reads the records only: a pod with similar_class < 0 or
+ * CA_POD_DAEMONSET is a group of its own; the pods of one similar class share a group, for the
+ * first 10 classes of a controller (class_owner[c], as in ca_filter_out_schedulable; ranked by
+ * the position of each class's first pod in the list, placed pods not counted); a pod of a
+ * later class is a group of its own every time it occurs.  class_owner NULL: no cap (n_classes
+ * is then ignored).  Groups are in the order of their first pods, the pods of a group in list
+ * order: the result is the same bytes on every call.  No pass over the pods runs on the host
+ * beyond the argument checks; the handle keeps the CSR in device memory and a host copy of it.
+ * CA_EINVAL, before any launch or allocation (no handle is left): n < 0; an order entry outside
+ * the pod set (order NULL: n above the pod set's size); class_owner given and a listed pod that
+ * can share a group has similar_class >= n_classes, or a class_owner entry is below 0.  There
+ * is no scope rule: the call simulates nothing. */
+typedef struct ca_pod_groups ca_pod_groups;
+int ca_pod_groups_create(ca_mirror* m, const ca_podset* s, const int32_t* order, int32_t n,
+                         const int32_t* node, const int32_t* class_owner, int32_t n_classes,
+                         ca_pod_groups** out);
+/* The number of groups and of pods in them.  Either pointer may be NULL. */
+int ca_pod_groups_info(const ca_pod_groups* g, int32_t* n_eg, int32_t* n_pods);
+/* eg_off[n_eg + 1] and eg_pod[n_pods] (pod-set indices); either may be NULL.  Group e's sample
+ * is eg_pod[eg_off[e]]. */
+int ca_pod_groups_fetch(const ca_pod_groups* g, int32_t* eg_off, int32_t* eg_pod);
+/* [0] the device time of the build in ms (HIP events around its launches, 0 for n == 0); [1] the
+ * number of kernels it launched (a function of n and of class_owner != NULL, not of the data).
+ * Writes min(cap, 2) values; returns 2. */
+int ca_pod_groups_timings(const ca_pod_groups* g, float* out, int32_t cap);
+int ca_pod_groups_destroy(ca_pod_groups* g);
+/* ca_expansion_plan_run with the samples of the groups (one per group, in group order) read
+ * from the handle's device memory: out / out_ok are [n_templates][n_eg].  g must have been built
+ * on s. */
+int ca_expansion_plan_run_groups(ca_expansion_plan* p, const ca_podset* s, const ca_pod_groups* g,
+                                 ca_pred_result* out, uint8_t* out_ok);
+/* ca_estimate_plan_create_options with eg_off / eg_pod / n_eg taken from the handle: the CSR is
+ * read where it lies in device memory (no upload, no per-item check; ok is all that crosses).
+ * The plan is the one ca_estimate_plan_create_options builds from ca_pod_groups_fetch's arrays,
+ * byte for byte.  CA_EINVAL: g not built on (m, s); a total item count that does not fit int32. */
+int ca_estimate_plan_create_groups(ca_mirror* m, const ca_podset* s, const ca_pod_groups* g,
+                                   const uint8_t* ok, const ca_template* templates, int32_t n_groups,
+                                   int32_t* group_off_out, ca_estimate_plan** out);
 int ca_estimate_plan_run(ca_estimate_plan* p, const ca_limiter* limiter, int32_t* last_index,
                          ca_estimate_result* results, int32_t* sched_pod, int32_t* sched_node);
 /* sched_pod == NULL (and sched_node == NULL) in ca_estimate_plan_run keeps the scheduled
