@@ -21,6 +21,8 @@ CA_EXPANDER_MOST_PODS, CA_EXPANDER_LEAST_WASTE = 1, 2     # ca_expander_best_opt
 # k_option_lists (estimate.hip OPT_TILE / OPT_CHUNK): output positions of one group per
 # workgroup, and pod equivalence groups per partial sum (tests place their cases at both)
 OPTION_LIST_TILE, OPTION_LIST_CHUNK = 2048, 256
+# k_cls_hist (estimate.hip CLS_HIST_TILE): positions of one list per workgroup
+CLS_HIST_TILE = 4096
 
 # podgroups.hip PG_TILE: positions of the pending list per workgroup pass of ca_pod_groups_create
 POD_GROUP_TILE = 2048

@@ -14,9 +14,11 @@
 //                                        run for the class's first group; writes the
 //                                        Go-order pod ids and that group's epoch-stamped
 //                                        ready flag, which the other members' consumers read.
-//   st  (heavy groups)   k_run_table     class ranks + per-class counts of each group's
-//                                        list, each rank's first stream position, the
-//                                        class's stream record against the template.
+//   (plan creation)      k_cls_hist      per-class counts of each group's list, once: the
+//                                        lists never change after creation.
+//   st  (heavy groups)   k_run_table     class ranks, the plan's counts by rank, each rank's
+//                                        first stream position, the class's stream record
+//                                        against the template.
 //                        k_ffd_chain     one 4-wave workgroup per group: the sequential
 //                                        First-Fit-Decreasing loop (per pod, or per run of
 //                                        identical pods in closed form) with the new-node
@@ -28,7 +30,8 @@
 //   st2 (light groups)   the same kernels for the groups outside the heavy set.
 //   pub_stream           k_publish       claims tickets in completion order and writes the
 //                                        scheduled pods (Go-order ids) into the caller's
-//                                        page-locked buffer while the chains run.
+//                                        page-locked buffer while the chains run; a ticket
+//                                        waits for the sort parts its positions lie in.
 //   host                 lastIndex fix-up: groups whose result depends on their lastIndex
 //                        input are re-run until every input equals its predecessor's
 //                        output (exact); the host joins the streams.
@@ -637,9 +640,70 @@ __global__ void __launch_bounds__(RTHREADS) k_radix_scatter(const GroupMeta* __r
 // needed: decoupled chains emit stream positions and the consumers map them through the
 // Go-order ids.
 #ifdef CASIM_PROF
-// k_run_table phase cycles per group slot (< 1024): ranking, counting, scan, records
-__device__ unsigned long long g_rt_prof[1024][4];
+// k_run_table phase cycles per group slot (< 1024): ranking, counts by rank + scan, records
+__device__ unsigned long long g_rt_prof[1024][3];
 #endif
+// Class counts of every group's list, cls_cnt[g][c] (indexed by class, not by rank), once
+// per plan: the lists are written at plan creation and never change, so the pass over them
+// does not belong in front of every run's heaviest chain.  One workgroup per tile of
+// CLS_HIST_TILE positions of one group; each wave counts a contiguous quarter of the tile,
+// 64 positions per step, adding a run of equal classes up in a register (classes come in
+// runs) and touching the workgroup's LDS histogram once per run; one global atomicAdd per
+// class present in the tile.  The table is zeroed on the same stream ahead of the launch.
+constexpr int CLS_HIST_TILE = 4096;    // (abi.CLS_HIST_TILE)
+__global__ void __launch_bounds__(256) k_cls_hist(const GroupMeta* __restrict__ groups,
+                                                 const int32_t* __restrict__ item_cls, int32_t U,
+                                                 int32_t* __restrict__ cls_cnt) {
+    __shared__ int32_t h[CLS_MAX];
+    const GroupMeta gm = groups[blockIdx.y];
+    const int32_t base = (int32_t)blockIdx.x * CLS_HIST_TILE;
+    if (base >= gm.count) return;                                   // (uniform per block)
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    for (int c = tid; c < U; c += 256) h[c] = 0;
+    __syncthreads();
+    constexpr int PER_W = CLS_HIST_TILE / 4, STEPS = PER_W / 64;
+    const int32_t end = min(gm.count, base + CLS_HIST_TILE);
+    const int32_t wb0 = min(end, base + w * PER_W), wb1 = min(end, wb0 + PER_W);
+    int32_t cv[STEPS];
+#pragma unroll
+    for (int u = 0; u < STEPS; u++) {
+        const int32_t i = wb0 + u * 64 + lane;
+        cv[u] = i < wb1 ? item_cls[gm.off + i] : -1;
+    }
+    int32_t cur = -1, acc = 0;                // (wave-uniform) the run being added up
+#pragma unroll
+    for (int u = 0; u < STEPS; u++) {
+        const bool valid = cv[u] >= 0 && cv[u] < U;
+        const int32_t c = cv[u];
+        const uint64_t vm = __ballot(valid);
+        if (!vm) continue;
+        const int32_t c0 = __builtin_amdgcn_readlane(c, __builtin_ctzll(vm));
+        if (__ballot(valid && c != c0) == 0) {          // one class in this step
+            if (c0 == cur) {
+                acc += __builtin_popcountll(vm);
+            } else {
+                if (acc > 0 && lane == 0) atomicAdd(&h[cur], acc);
+                cur = c0;
+                acc = __builtin_popcountll(vm);
+            }
+            continue;
+        }
+        uint64_t act = vm;                                // a class boundary in the step
+        while (act) {
+            const int l = __builtin_ctzll(act);
+            const int32_t cl = __builtin_amdgcn_readlane(c, l);
+            const uint64_t m = __ballot(valid && c == cl) & act;
+            if (lane == l) atomicAdd(&h[cl], __builtin_popcountll(m));
+            act &= ~m;
+        }
+    }
+    if (acc > 0 && lane == 0) atomicAdd(&h[cur], acc);
+    __syncthreads();
+    int32_t* out = cls_cnt + (size_t)blockIdx.y * U;
+    for (int c = tid; c < U; c += 256)
+        if (h[c] > 0) atomicAdd(&out[c], h[c]);
+}
+
 __device__ inline int32_t run_rank(const int32_t* __restrict__ st, int32_t U, int32_t i) {
     int32_t lo = 0, hi = U;                  // the last r with st[r] <= i (st[U] is never read)
     while (hi - lo > 1) {
@@ -650,7 +714,7 @@ __device__ inline int32_t run_rank(const int32_t* __restrict__ st, int32_t U, in
 }
 
 __global__ void __launch_bounds__(1024) k_run_table(const GroupMeta* __restrict__ groups,
-                                                   const int32_t* __restrict__ item_cls,
+                                                   const int32_t* __restrict__ cls_cnt,
                                                    const int64_t* __restrict__ cls_sc, int32_t NP,
                                                    const int32_t* __restrict__ cls_rep,
                                                    int32_t U, const ca_template* __restrict__ tmpls,
@@ -676,81 +740,36 @@ __global__ void __launch_bounds__(1024) k_run_table(const GroupMeta* __restrict_
 #ifdef CASIM_PROF
     const uint64_t t_r0 = clock64();
 #endif
-    // Each wave counts a contiguous region of the list, 64 positions per step (classes come
-    // in runs: a wave adds a run to a register and touches the LDS counter once per run —
-    // with every wave on a strided slice the same few counters took ~1 000 contended LDS
-    // atomics per group).  The class scores (ranking, up to 64 classes) are requested
-    // first and the region's first RUB steps right after — all of a C2 group's list (up to
-    // 64 x 64 x 16 positions) — so the ranking waits only for the scores.  (Measured,
-    // CASIM_PROF: counting stays ~40k of the kernel's ~65k cycles whether the loads go in
-    // slices or all at once, and with strided or contiguous slices — not memory latency,
-    // not the LDS atomics)
-    constexpr int RUB = 64;
-    const int32_t per_w = ((gm.count + 15) / 16 + 63) & ~63;
-    const int32_t wb0 = min(gm.count, w * per_w), wb1 = min(gm.count, wb0 + per_w);
+    // The class counts of the group's list come from the plan (k_cls_hist, once at creation:
+    // the list pass took ~40k of this kernel's ~65k cycles in front of the heaviest chain,
+    // DESIGN §8).  They are requested first, with the class scores (ranking, up to 64
+    // classes), so the ranking waits only for the scores.
     const bool small = NP <= 64;
     int64_t s_cpu = 0, s_mem = 0;
     if (small && tid < U) { s_cpu = cls_sc[2 * tid]; s_mem = cls_sc[2 * tid + 1]; }
-    int32_t cv[RUB];
+    const int32_t* gcnt = cls_cnt + (size_t)gi * U;
+    int32_t my[CLS_MAX / 1024];               // classes tid, tid + 1024, ...
 #pragma unroll
-    for (int u = 0; u < RUB; u++) {
-        const int32_t i = wb0 + u * 64 + lane;
-        cv[u] = i < wb1 ? item_cls[gm.off + i] : -1;
+    for (int q = 0; q < CLS_MAX / 1024; q++) {
+        const int c = tid + q * 1024;
+        my[q] = c < U ? gcnt[c] : 0;
     }
     if (small) wave_class_rank(tmpls[gm.tmpl], s_cpu, s_mem, U, NP, key, idx, rc);   // (rc: scratch)
     else block_class_rank(tmpls[gm.tmpl], cls_sc, U, NP, key, idx, rc);
     for (int i = tid; i < U; i += 1024) cr[idx[i]] = rc[i];
     __syncthreads();
-    for (int i = tid; i < U; i += 1024) { cnt[i] = 0; rc[i] = 0; }
+#pragma unroll
+    for (int q = 0; q < CLS_MAX / 1024; q++) {
+        const int c = tid + q * 1024;
+        if (c < U) { cnt[c] = my[q]; rc[c] = 0; }
+    }
     __syncthreads();
 #ifdef CASIM_PROF
     const uint64_t t_r1 = clock64();
 #endif
-    // class counts over the wave's region
-    int32_t cur = -1, acc = 0;                // (wave-uniform) the run being added up
-    for (int32_t base = wb0; base < wb1; base += 64 * RUB) {
-        if (base > wb0) {                     // (groups past 65 536 positions)
-#pragma unroll
-            for (int u = 0; u < RUB; u++) {
-                const int32_t i = base + u * 64 + lane;
-                cv[u] = i < wb1 ? item_cls[gm.off + i] : -1;
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < RUB; u++) {
-            const bool valid = cv[u] >= 0;
-            const int32_t c = cv[u];
-            const uint64_t vm = __ballot(valid);
-            if (!vm) continue;
-            const int32_t c0 = __builtin_amdgcn_readlane(c, __builtin_ctzll(vm));
-            if (__ballot(valid && c != c0) == 0) {          // one class in this step
-                if (c0 == cur) {
-                    acc += __builtin_popcountll(vm);
-                } else {
-                    if (acc > 0 && lane == 0) atomicAdd(&cnt[cur], acc);
-                    cur = c0;
-                    acc = __builtin_popcountll(vm);
-                }
-                continue;
-            }
-            uint64_t act = vm;                                // a class boundary in the step
-            while (act) {
-                const int l = __builtin_ctzll(act);
-                const int32_t cl = __builtin_amdgcn_readlane(c, l);
-                const uint64_t m = __ballot(valid && c == cl) & act;
-                if (lane == l) atomicAdd(&cnt[cl], __builtin_popcountll(m));
-                act &= ~m;
-            }
-        }
-    }
-    if (acc > 0 && lane == 0) atomicAdd(&cnt[cur], acc);
-    __syncthreads();
     for (int c = tid; c < U; c += 1024)
         if (cnt[c] > 0) atomicAdd(&rc[cr[c]], cnt[c]);
     __syncthreads();
-#ifdef CASIM_PROF
-    const uint64_t t_r2 = clock64();
-#endif
     // exclusive scan of the counts by rank: thread t owns ranks [4t, 4t + 4)
     int32_t v[4], loc = 0;
     for (int q = 0; q < 4; q++) { const int r = 4 * tid + q; v[q] = r < U ? rc[r] : 0; loc += v[q]; }
@@ -796,8 +815,7 @@ __global__ void __launch_bounds__(1024) k_run_table(const GroupMeta* __restrict_
 #ifdef CASIM_PROF
         if (gi < 1024) {
             const uint64_t t_r4 = clock64();
-            g_rt_prof[gi][0] = t_r1 - t_r0; g_rt_prof[gi][1] = t_r2 - t_r1;
-            g_rt_prof[gi][2] = t_r3 - t_r2; g_rt_prof[gi][3] = t_r4 - t_r3;
+            g_rt_prof[gi][0] = t_r1 - t_r0; g_rt_prof[gi][1] = t_r3 - t_r1; g_rt_prof[gi][2] = t_r4 - t_r3;
         }
 #endif
     }
@@ -1645,6 +1663,55 @@ __device__ inline Seg ld_seg(const Seg* p) {
 // died).  qctl[2] sends the host to the stream-ordered copy (k_copy_segments + D2H).
 // T = int32_t: pod ids; T = uint16_t: pod ids of a podset of at most 65535 pods, 0xFFFF for
 // "not scheduled" (ca_estimate_plan_run_u16: half the bytes over PCIe).
+
+// first segment of gs[0, nseg) that ends after `key` (from_dst false) or starts at or after
+// it (true); segments are in output order.  One wavefront probes 64 evenly spaced segments
+// per step with coherent loads in flight together, so a search is one or two round trips
+// to L2 instead of one per bisection step.
+__device__ inline int32_t seg_lower(const Seg* gs, int32_t nseg, int32_t key, bool from_dst, int lane) {
+    int32_t lo = 0, hi = nseg;                     // answer in [lo, hi]
+    while (hi - lo > 0) {
+        const int32_t span = hi - lo;
+        const int32_t step = (span + 63) / 64;
+        const int32_t i = lo + lane * step;
+        bool past = false;
+        if (i < hi) {
+            const int32_t* q3 = reinterpret_cast<const int32_t*>(gs + i);
+            past = from_dst ? ld_coh(q3) >= key : ld_coh(q3) + ld_coh(q3 + 2) > key;
+        }
+        const uint64_t m = __ballot(past);
+        const int32_t f = m ? (int32_t)__builtin_ctzll(m) : -1;    // first probe past the key
+        if (step == 1) { lo = f >= 0 ? lo + f : hi; break; }
+        const int32_t nlo = f > 0 ? lo + (f - 1) * step + 1 : (f == 0 ? lo : lo + ((span - 1) / step) * step + 1);
+        hi = f >= 0 ? lo + f * step : hi;
+        lo = nlo;
+    }
+    return lo;
+}
+__device__ inline int32_t bc32(int32_t v) { return (int32_t)__builtin_amdgcn_readfirstlane((uint32_t)v); }
+__device__ inline int64_t bc64(int64_t v) {
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)(uint64_t)v);
+    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)((uint64_t)v >> 32));
+    return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+// (the helpers below read a whole fan record with one load per wavefront and index it by lane)
+static_assert(pdq::FAN_STRIDE <= 64 && pdq::FAN_FLAG == 0 && pdq::FAN_PARTS_MAX <= 32, "fan record: one word per lane, flags first");
+static_assert(pdq::FAN_LO + pdq::FAN_PARTS_MAX < pdq::FAN_STRIDE && pdq::FAN_BOUNDS < pdq::FAN_STRIDE &&
+              pdq::FAN_NPARTS < pdq::FAN_STRIDE, "fan record: bounds inside the loaded words");
+// a sort's fan record (pdq::FAN_STRIDE words), word `lane` in each lane
+__device__ inline int32_t fan_load(const int32_t* fr, int lane) {
+    return lane < pdq::FAN_STRIDE ? ld_coh(fr + lane) : 0;
+}
+// the parts of a sort that overlap Go-order positions [s0, s1), from a record whose bounds are final
+__device__ inline uint32_t fan_need(int32_t v, int lane, int32_t s0, int32_t s1) {
+    const int32_t np = min(rl32(v, pdq::FAN_NPARTS), (int32_t)pdq::FAN_PARTS_MAX);
+    const int32_t lo0 = __shfl(v, min(pdq::FAN_LO + lane, 63)), lo1 = __shfl(v, min(pdq::FAN_LO + lane + 1, 63));
+    return (uint32_t)__ballot(lane < np && lo0 < s1 && lo1 > s0);
+}
+__device__ inline uint32_t fan_up(int32_t v, int lane, int32_t epoch) {
+    return (uint32_t)__ballot(lane < pdq::FAN_PARTS_MAX && v == epoch);
+}
+
 template <typename T>
 __global__ void __launch_bounds__(256) k_publish(const GroupMeta* __restrict__ groups, const ChainOut* __restrict__ outs,
                                                 const Seg* __restrict__ segs, const int32_t* __restrict__ spod,
@@ -1655,97 +1722,123 @@ __global__ void __launch_bounds__(256) k_publish(const GroupMeta* __restrict__ g
                                                 uint64_t start_ticks, const int32_t* ids_ready, int32_t ids_epoch,
                                                 int32_t* __restrict__ hflags) {
     // ids_ready != null (decoupled Go order): the stream's pod ids in spod
-    // come from a sort that runs beside the chains — a group's are final once
-    // ids_ready[g] holds this run's epoch — and the chains' single placements are stream positions
-    __shared__ int32_t s_t, s_seg0;
+    // come from a sort that runs beside the chains — the fan record of the group whose sort
+    // wrote them (the group's own, or the representative of its sort class) flags each part
+    // of the Go order with this run's epoch once its ids are final — and the chains' single
+    // placements are stream positions.  A ticket reads Go-order positions [s0, s1) of that
+    // sort and waits for the parts that overlap them:
+    //   a pure chunk          its own slice;
+    //   a segment ticket      from the first to the last position its segments read — the
+    //                         chain walks the stream forwards, so the first and the last
+    //                         segment that overlap the chunk bound them;
+    //   a group with single   every part: a single placement indexes any position (the
+    //   steps so far          chain sets the sign bit of the progress record's nseg).
+    // The bounds are final once FAN_BOUNDS holds this run's epoch; a flag seen up stays up.
+    // Wave 0 is the block's controller (the other waves sleep at the barrier): it claims the
+    // ticket, waits for its push, finds its positions and polls the sort's fan record — 40
+    // words, one load — until the parts it needs are up.
+    __shared__ int32_t s_seg0;
     __shared__ int64_t s_tk;
     __shared__ Seg s_segs[64];
+    const int lane = (int)threadIdx.x & 63;
+    bool gave_up = false;                      // (wave 0)
     for (;;) {
-        if (threadIdx.x == 0) {
-            s_t = atomicAdd(&qctl[0], 1);
+        if (threadIdx.x < 64) {
             int64_t tk = -1;
-            if (s_t < total) {
+            int32_t seg0 = 0, t = 0;
+            if (lane == 0) t = atomicAdd(&qctl[0], 1);
+            t = bc32(t);
+            if (t < total) {
                 const uint64_t t0 = wall_clock64();
                 bool started = false;
                 for (;;) {
                     // relaxed polls (an acquire per poll invalidates caches other kernels on
                     // the XCD are using); the acquire comes once, when the ticket is there
-                    tk = __hip_atomic_load(&tickets[s_t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    tk = bc64(__hip_atomic_load(&tickets[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
                     if (tk >= 0) {      // consumed: the slot is -1 again for the next run
                         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                        __hip_atomic_store(&tickets[s_t], -1ll, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        if (lane == 0) __hip_atomic_store(&tickets[t], -1ll, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                         break;
                     }
-                    if (__hip_atomic_load(&qctl[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break;  // given up
-                    if (!started) started = __hip_atomic_load(&qctl[4], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
+                    if (bc32(__hip_atomic_load(&qctl[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) { gave_up = true; break; }
+                    if (!started) started = bc32(__hip_atomic_load(&qctl[4], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) != 0;
                     const uint64_t dt = wall_clock64() - t0;
                     if ((!started && dt > start_ticks) || dt > 20000000ull) {               // 200 ms
-                        __hip_atomic_store(&qctl[2], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        if (lane == 0) __hip_atomic_store(&qctl[2], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        gave_up = true;
                         break;
                     }
                     __builtin_amdgcn_s_sleep(2);
                 }
-                if (tk >= 0 && ids_ready) {                  // the group's Go-order ids
-                    // (the fan record of the group whose sort wrote them: the group's own, or
-                    // the representative of its sort class.)  The ticket reads Go-order
-                    // positions [s0, s1) of that sort — a pure chunk its own slice; a segment
-                    // ticket any position (single placements index the whole list), so every
-                    // part — and waits for the parts that overlap them.  The bounds are final
-                    // once FAN_BOUNDS holds this run's epoch; a flag seen up stays up, so the
-                    // flags are polled together with it (one round trip when all is ready).
+                if (tk >= 0) {
                     const int32_t tkid = (int32_t)(uint32_t)(tk & 0xFFFFFFFFll);
                     const int32_t g0 = tkid / nsub;
-                    const int32_t* fr = ids_ready + (size_t)groups[g0].ids_grp * pdq::FAN_STRIDE;
-                    uint32_t up = 0, need = 0;
-                    bool bounds = false;
-                    for (;;) {
-                        int32_t fv[pdq::FAN_PARTS_MAX];
-#pragma unroll
-                        for (int j = 0; j < pdq::FAN_PARTS_MAX; j++) fv[j] = ld_coh(fr + pdq::FAN_FLAG + j);
-                        const bool bnow = bounds || ld_coh(fr + pdq::FAN_BOUNDS) == ids_epoch;
-#pragma unroll
-                        for (int j = 0; j < pdq::FAN_PARTS_MAX; j++) up |= fv[j] == ids_epoch ? 1u << j : 0u;
-                        if (bnow && !bounds) {
-                            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                            bounds = true;
-                            int32_t lo[pdq::FAN_PARTS_MAX + 1];
-#pragma unroll
-                            for (int j = 0; j <= pdq::FAN_PARTS_MAX; j++) lo[j] = ld_coh(fr + pdq::FAN_LO + j);
-                            const int32_t np = min(ld_coh(fr + pdq::FAN_NPARTS), (int32_t)pdq::FAN_PARTS_MAX);
-                            int32_t s0 = 0, s1 = INT32_MAX;
-                            const int32_t po = (int32_t)(tk >> 32) - 1;
-                            if (po >= 0) {
-                                const int32_t a = (tkid - g0 * nsub) * pch;
-                                s0 = po + a;
-                                s1 = po + min(groups[g0].count, a + pch);
+                    const int32_t a = (tkid - g0 * nsub) * pch, b = min(groups[g0].count, a + pch);
+                    const int32_t po = (int32_t)(tk >> 32) - 1;
+                    int32_t s0 = 0, s1 = INT32_MAX;
+                    if (po >= 0) {
+                        s0 = po + a;
+                        s1 = po + b;
+                    } else {
+                        const int32_t* pr = reinterpret_cast<const int32_t*>(prog + tkid);   // progress at the push
+                        const int32_t nsw = bc32(ld_coh(pr));
+                        const int32_t end = min(b, bc32(ld_coh(pr + 1)));
+                        const int32_t nseg = nsw & INT32_MAX;
+                        const Seg* gs = segs + groups[g0].off;
+                        seg0 = seg_lower(gs, nseg, a, false, lane);
+                        if (ids_ready && nsw >= 0) {
+                            if (end <= a) {
+                                s0 = s1 = 0;                         // the -1 tail alone: no ids
+                            } else {
+                                const int32_t q1 = seg_lower(gs, nseg, end, true, lane);
+                                if (seg0 < q1) {
+                                    const Seg f = ld_seg(gs + seg0), l = ld_seg(gs + q1 - 1);
+                                    s0 = bc32(f.src - f.dst + max(a, f.dst));
+                                    s1 = bc32(l.src - l.dst + min(end, l.dst + l.len));
+                                }
                             }
-#pragma unroll
-                            for (int j = 0; j < pdq::FAN_PARTS_MAX; j++)
-                                if (j < np && lo[j] < s1 && lo[j + 1] > s0) need |= 1u << j;
                         }
-                        if (bounds && (need & ~up) == 0) {
-                            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                            break;
+                    }
+                    if (ids_ready && s0 < s1) {
+                        const int32_t* fr = ids_ready + (size_t)groups[g0].ids_grp * pdq::FAN_STRIDE;
+                        bool bounds = false;
+                        uint32_t need = 0;
+                        for (;;) {
+                            int32_t v = fan_load(fr, lane);
+                            if (!bounds && rl32(v, pdq::FAN_BOUNDS) == ids_epoch) {
+                                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+                                v = fan_load(fr, lane);                  // (the bounds, read behind the acquire)
+                                need = fan_need(v, lane, s0, s1);
+                                bounds = true;
+                            }
+                            if (bounds && (need & ~fan_up(v, lane, ids_epoch)) == 0) {
+                                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+                                break;
+                            }
+                            if (bc32(__hip_atomic_load(&qctl[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) {
+                                gave_up = true;
+                                tk = -1;
+                                break;
+                            }
+                            if (wall_clock64() - t0 > 20000000ull) {                            // 200 ms
+                                if (lane == 0) __hip_atomic_store(&qctl[2], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                                gave_up = true;
+                                tk = -1;
+                                break;
+                            }
+                            __builtin_amdgcn_s_sleep(2);
                         }
-                        if (__hip_atomic_load(&qctl[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) { tk = -1; break; }
-                        if (wall_clock64() - t0 > 20000000ull) {                            // 200 ms
-                            __hip_atomic_store(&qctl[2], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            tk = -1;
-                            break;
-                        }
-                        __builtin_amdgcn_s_sleep(2);
                     }
                 }
             }
-            s_tk = tk;
+            if (lane == 0) { s_tk = tk; s_seg0 = seg0; }
         }
         lds_barrier();
-        const int32_t t = s_t;
         const int64_t tk64 = s_tk;
-        if (t >= total || tk64 < 0) {
+        if (tk64 < 0) {
             if (threadIdx.x == 0) {
                 // gave up (qctl[2]): tell the host, which reads hflags after the round (no copy)
-                if (t < total) hflags[2] = 1;
+                if (gave_up) hflags[2] = 1;
                 // the last block out clears the control words for the next run (every ticket
                 // was consumed, so no chain pushes any more; after a give-up the host
                 // re-initialises them)
@@ -1786,33 +1879,8 @@ __global__ void __launch_bounds__(256) k_publish(const GroupMeta* __restrict__ g
             continue;
         }
         const int32_t* pr = reinterpret_cast<const int32_t*>(prog + tk);   // the group's progress at the push
-        const int32_t nseg = ld_coh(pr);
+        const int32_t nseg = ld_coh(pr) & INT32_MAX;       // (sign bit: the group made single steps)
         const int32_t ns = ld_coh(pr + 1);
-        if (threadIdx.x < 64) {
-            // first segment ending after a (segments are in output order): wave 0 probes 64
-            // evenly spaced segments per step with coherent loads in flight together, so a
-            // search is one or two round trips to L2 instead of one per bisection step
-            const int lane = (int)threadIdx.x;
-            int32_t lo = 0, hi = nseg;                     // answer in [lo, hi]
-            while (hi - lo > 0) {
-                const int32_t span = hi - lo;
-                const int32_t step = (span + 63) / 64;
-                const int32_t i = lo + lane * step;
-                bool past = false;                         // segment i ends after a
-                if (i < hi) {
-                    const int32_t* q3 = reinterpret_cast<const int32_t*>(gs + i);
-                    past = ld_coh(q3) + ld_coh(q3 + 2) > a;
-                }
-                const uint64_t m = __ballot(past);
-                const int32_t f = m ? (int32_t)__builtin_ctzll(m) : -1;    // first probe past a
-                if (step == 1) { lo = f >= 0 ? lo + f : hi; break; }
-                const int32_t nlo = f > 0 ? lo + (f - 1) * step + 1 : (f == 0 ? lo : lo + ((span - 1) / step) * step + 1);
-                hi = f >= 0 ? lo + f * step : hi;
-                lo = nlo;
-            }
-            if (lane == 0) s_seg0 = lo;
-        }
-        lds_barrier();
         int32_t at = a, q = s_seg0;
         const int32_t end = min(b, ns);
         int32_t q0 = 0, qn = 0;                           // segments [q0, q0 + qn) cached in LDS
@@ -2057,7 +2125,8 @@ __global__ void __launch_bounds__(CT) k_ffd_chain(
             so_pod[out_idx] = (TB || pos_out) ? wbase + lane : cur.pod;
             pend = false;
         }
-        push_chunks(g, tk_next, c1, nsub, tickets, qctl, prog, nseg, nsched, lane, pch, pure_from, pure_off);
+        push_chunks(g, tk_next, c1, nsub, tickets, qctl, prog, nseg | (n_single ? INT32_MIN : 0), nsched, lane, pch, pure_from,
+                    pure_off);
         tk_next = c1;
     };
 
@@ -2711,7 +2780,8 @@ __global__ void __launch_bounds__(CT) k_ffd_chain(
             // every pod scheduled: the tail chunks are pure when one segment offset covers them
             // (the publisher copies them straight from the stream's ids, no segment reads)
             const bool all = ok && nsched == P;
-            push_chunks(g, tk_next, (P + pch - 1) / pch, nsub, tickets, qctl, prog, ok ? nseg : 0, ok ? nsched : 0, lane,
+            push_chunks(g, tk_next, (P + pch - 1) / pch, nsub, tickets, qctl, prog,
+                        ok ? nseg | (n_single ? INT32_MIN : 0) : 0, ok ? nsched : 0, lane,
                         all ? pch : 0, all ? pure_from : INT32_MAX, pure_off);
         }
     }
@@ -2813,6 +2883,10 @@ struct ca_estimate_plan {
     DevBuf d_sortC, d_ids_ready, d_spod_go, d_crank2;
     DevBuf d_rstart, d_rsp;        // decoupled: per group, each rank's first stream position and record
     DevBuf d_item_cls;             // bucket path: the score class of every (group, pod) item, uploaded with the lists
+    // ... with uniform classes: [G][n_cls] items of each class in each list (k_cls_hist), in
+    // the tail of d_item_cls (one allocation: a hipMalloc costs more than the histogram)
+    bool has_cls_cnt = false;
+    int32_t* cls_cnt() const { return d_item_cls.as<int32_t>() + total; }
     float opt_lists_ms = 0.f;      // option form: device time of k_option_lists at creation (0 otherwise)
     int32_t ids_epoch = 0;
     // shared sorts (sort_classes): the number of sort classes — when below G their
@@ -3525,7 +3599,10 @@ int plan_prepare(ca_estimate_plan* p, ca_mirror* m, const ca_podset* s, const in
     if (G) CA_HIP_CHECK(hipMemcpyAsync(p->d_meta.ptr, p->h_meta.data(), sizeof(GroupMeta) * G, hipMemcpyHostToDevice, st));
     // the lists as (pod, class) pairs: the class of every item next to its pod index, so
     // the sorts and the run table read it in one coalesced load instead of two gathers
-    if (p->bucket && p->total > 0 && (rc = p->d_item_cls.reserve(sizeof(int32_t) * (size_t)p->total)) != CA_OK) return rc;
+    p->has_cls_cnt = p->bucket && s->cls_uniform && p->total > 0;
+    if (p->bucket && p->total > 0 &&
+        (rc = p->d_item_cls.reserve(sizeof(int32_t) * ((size_t)p->total + (p->has_cls_cnt ? (size_t)G * (size_t)s->n_cls : 0)))) != CA_OK)
+        return rc;
     DevBuf d_eg_off, d_eg_pod, d_ok, d_chunk_pre;      // option form: alive until the stream is drained below
     if (opt) {
         // the lists are built in HBM from the equivalence groups and the matrix: 4 B per
@@ -3562,6 +3639,14 @@ int plan_prepare(ca_estimate_plan* p, ca_mirror* m, const ca_podset* s, const in
         const int32_t nb = (int32_t)std::min<int64_t>(4096, (p->total + 255) / 256);
         hipLaunchKernelGGL(k_item_cls, dim3(nb), dim3(256), 0, st, p->d_pod_idx.as<int32_t>(),
                            s->d_cls.as<int32_t>(), p->d_item_cls.as<int32_t>(), p->total);
+        CA_HIP_CHECK(hipGetLastError());
+    }
+    // the class counts of every list, behind whichever kernel wrote the classes: plans that
+    // can take the run-table path (k_run_table reads them in every run)
+    if (p->has_cls_cnt) {
+        CA_HIP_CHECK(hipMemsetAsync(p->cls_cnt(), 0, sizeof(int32_t) * (size_t)G * (size_t)s->n_cls, st));
+        hipLaunchKernelGGL(k_cls_hist, dim3((p->max_count + CLS_HIST_TILE - 1) / CLS_HIST_TILE, G), dim3(256), 0, st,
+                           p->d_meta.as<GroupMeta>(), p->d_item_cls.as<int32_t>(), s->n_cls, p->cls_cnt());
         CA_HIP_CHECK(hipGetLastError());
     }
     if (G) CA_HIP_CHECK(hipMemcpyAsync(p->d_tmpl.ptr, templates, sizeof(ca_template) * G, hipMemcpyHostToDevice, st));
@@ -3907,11 +3992,13 @@ int plan_run(ca_estimate_plan* p, const ca_limiter* lim, int32_t* last_index, ca
         gmapB = gmapA + p->n_heavy;
     }
     const int32_t nA = split ? p->n_heavy : G, nB = split ? G - p->n_heavy : 0;
-    // With the run-table chain the heavy chains end ~60 us before the publisher does (C2:
-    // profiles/table_chain_timeline.txt): the step's end is the Go-order sort's end plus the
-    // ~110 us the publisher then needs for the chunks that waited for their ids, so the sort
-    // is launched first and the heavy run table right behind it.  On the stream path the
-    // heavy chains bound the step and go first.  (CASIM_SORT_FIRST=1 / 0 forces either.)
+    // With the run-table chain the sort is launched first and the heavy run table right behind
+    // it.  Since a segment ticket waits only for the sort parts it reads and k_run_table takes
+    // its counts from the plan, the publisher ends ~5 us after the heavy chain and the step
+    // ends with that chain (C2: profiles/publish_hold_timeline.txt); launching the heavy
+    // chains first measured 0.007-0.011 ms faster in every round but cleared the A/B rule in
+    // one record of three (profiles/publish_hold_ab.txt), so the order stays.  On the stream
+    // path the heavy chains bound the step and go first.  (CASIM_SORT_FIRST=1 / 0 forces either.)
     const char* sf_env = knob_env("CASIM_SORT_FIRST");
     const bool sort_first = sf_env ? atoi(sf_env) != 0 : table_chain;
     const bool sort_after_heavy = split && p->total > 0 && p->bucket && !sort_first;
@@ -3944,7 +4031,7 @@ int plan_run(ca_estimate_plan* p, const ca_limiter* lim, int32_t* last_index, ca
                 // are computed inside k_run_table)
                 if (events && p->phase_events) CA_HIP_CHECK(hipEventRecord(p->ev[ca_estimate_plan::EV_SCORE], ss));
                 hipLaunchKernelGGL(k_run_table, dim3(ng), dim3(1024), 0, ss, p->d_meta.as<GroupMeta>(),
-                                   p->d_item_cls.as<int32_t>(), p->s->d_cls_sc.as<int64_t>(), NP,
+                                   p->cls_cnt(), p->s->d_cls_sc.as<int64_t>(), NP,
                                    p->s->d_cls_rep.as<int32_t>(), U,
                                    p->d_tmpl.as<ca_template>(), p->s->t.hot.as<PodHot>(), p->s->t.spec.as<ca_pod_spec>(),
                                    p->s->t.terms.as<ca_selector_term>(), p->s->t.reqs.as<ca_selector_req>(),
@@ -4500,6 +4587,21 @@ int ca_estimate_plan_fetch_lists(const ca_estimate_plan* p, int32_t* pod_idx, in
     return CA_OK;
 }
 
+int ca_estimate_plan_fetch_class_counts(const ca_estimate_plan* p, int32_t* out, int32_t* n_classes) {
+    if (!p || (!out && !n_classes)) return CA_EINVAL;
+    if (n_classes) *n_classes = p->s->n_cls;
+    if (!out) return CA_OK;
+    CA_HIP_CHECK(hipSetDevice(p->m->device));
+    const size_t n = (size_t)p->G * (size_t)p->s->n_cls;
+    if (!p->has_cls_cnt) {                 // (no items, or a plan that never takes the run-table path)
+        if (p->total > 0) return CA_EINVAL;
+        std::fill(out, out + n, 0);
+        return CA_OK;
+    }
+    CA_HIP_CHECK(hipMemcpy(out, p->cls_cnt(), sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+    return CA_OK;
+}
+
 int ca_estimate_plan_fetch(const ca_estimate_plan* p, int32_t* sched_pod) {
     if (!p || !sched_pod) return CA_EINVAL;
     CA_HIP_CHECK(hipSetDevice(p->m->device));
@@ -4704,9 +4806,9 @@ int ca_debug_chain_prof(uint64_t* out, int32_t n_groups) {
     CA_HIP_CHECK(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_chain_prof), sizeof(uint64_t) * NPROF * (size_t)n_groups));
     return CA_OK;
 }
-int ca_debug_rt_prof(uint64_t* out, int32_t n_groups) {     // k_run_table phases: 4 per group
+int ca_debug_rt_prof(uint64_t* out, int32_t n_groups) {     // k_run_table phases: 3 per group
     if (n_groups > 1024) n_groups = 1024;
-    CA_HIP_CHECK(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_rt_prof), sizeof(uint64_t) * 4 * (size_t)n_groups));
+    CA_HIP_CHECK(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_rt_prof), sizeof(uint64_t) * 3 * (size_t)n_groups));
     return CA_OK;
 }
 #endif

@@ -93,6 +93,7 @@ def load() -> C.CDLL:
         "ca_estimate_plan_create": ([vp, vp, vp, vp, vp, i32, p(vp)], C.c_int),
         "ca_estimate_plan_create_options": ([vp, vp, vp, vp, i32, vp, vp, i32, vp, p(vp)], C.c_int),
         "ca_estimate_plan_fetch_lists": ([vp, vp, vp], C.c_int),
+        "ca_estimate_plan_fetch_class_counts": ([vp, vp, p(i32)], C.c_int),
         "ca_pod_groups_create": ([vp, vp, vp, i32, vp, vp, i32, p(vp)], C.c_int),
         "ca_pod_groups_info": ([vp, p(i32), p(i32)], C.c_int),
         "ca_pod_groups_fetch": ([vp, vp, vp], C.c_int),
@@ -226,7 +227,7 @@ def exported_symbols() -> list[str]:
         "ca_mirror_node_pods", "ca_podset_create", "ca_podset_destroy", "ca_fits_any_node", "ca_check_predicates",
         "ca_fits_matrix", "ca_check_templates", "ca_expansion_plan_create", "ca_expansion_plan_run",
         "ca_expansion_plan_destroy", "ca_expansion_plan_kernel_ms", "ca_estimate_batch", "ca_estimate_plan_create", "ca_estimate_plan_run",
-        "ca_estimate_plan_create_options", "ca_estimate_plan_fetch_lists",
+        "ca_estimate_plan_create_options", "ca_estimate_plan_fetch_lists", "ca_estimate_plan_fetch_class_counts",
         "ca_pod_groups_create", "ca_pod_groups_info", "ca_pod_groups_fetch", "ca_pod_groups_timings",
         "ca_pod_groups_destroy", "ca_expansion_plan_run_groups", "ca_estimate_plan_create_groups",
         "ca_estimate_plan_run_u16",
@@ -1120,6 +1121,15 @@ class EstimatePlan:
         _check(self.lib.ca_estimate_plan_fetch_lists(self.h, ptr(pod_idx), ptr(item_cls)), "ca_estimate_plan_fetch_lists")
         has_cls = self.total == 0 or bool((item_cls[: self.total] >= 0).all())
         return pod_idx[: self.total], (item_cls[: self.total] if has_cls else None)
+
+    def fetch_class_counts(self) -> np.ndarray:
+        """[G, U] items of each score class in each group's list, as the device counted them
+        when the plan was created (ca_estimate_plan_fetch_class_counts)."""
+        u = C.c_int32(0)
+        _check(self.lib.ca_estimate_plan_fetch_class_counts(self.h, None, C.byref(u)), "ca_estimate_plan_fetch_class_counts")
+        out = np.zeros(max(self.G * u.value, 1), np.int32)
+        _check(self.lib.ca_estimate_plan_fetch_class_counts(self.h, ptr(out), None), "ca_estimate_plan_fetch_class_counts")
+        return out[: self.G * u.value].reshape(self.G, u.value)
 
     def option_sums(self) -> tuple:
         """resourcesForPods (waste.go:74-87) of every group of the last run, summed on the

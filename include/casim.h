@@ -436,6 +436,14 @@ int ca_estimate_plan_create_options(ca_mirror* m, const ca_podset* s,
  * checks): pod_idx[total] and the score class of every item, item_cls[total].  Either may be
  * NULL.  item_cls exists on the bucket path only; otherwise it is left untouched. */
 int ca_estimate_plan_fetch_lists(const ca_estimate_plan* p, int32_t* pod_idx, int32_t* item_cls);
+/* The class counts the plan keeps beside its lists (for tests and Go-side checks):
+ * out[g * U + c] = items of group g's list whose pod is of score class c, U = *n_classes the
+ * podset's score classes.  The device counts them once, when the plan is created, for plans
+ * on the bucket path whose podset has uniform classes (the run table of every run starts
+ * from them); any other plan with items answers CA_EINVAL, a plan without items all zeros.
+ * out NULL: only *n_classes is written (the row length to allocate for); n_classes may be
+ * NULL otherwise. */
+int ca_estimate_plan_fetch_class_counts(const ca_estimate_plan* p, int32_t* out, int32_t* n_classes);
 
 /* Pod equivalence groups built in device memory (equivalence.BuildPodGroups,
  * core/scaleup/equivalence/groups.go:38-102), the input of the two calls above and of
