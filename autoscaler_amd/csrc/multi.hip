@@ -13,6 +13,8 @@
 // After a resident Estimate run the one-device readers of ScaleUp (option sums, price sums,
 // one group's list, filterNodeGroupsByPods) work over the blocks; the last of them is the
 // only call that moves list data from one device to another (through host memory).
+// The Estimate plan is created from the groups' pod lists, or from the option matrix (the pod
+// equivalence groups and the verdicts): every block then builds its own lists on its device.
 #include <algorithm>
 #include <thread>
 #include <chrono>
@@ -172,6 +174,118 @@ int ca_multi_estimate_plan_create(ca_multi* mm, const ca_pod_table* t, const int
     if (rc != CA_OK) { delete p; return rc; }
     *out = p;
     return CA_OK;
+}
+
+// The plan from the option matrix (DESIGN.md §6 "ScaleUp on sharded plans"): the blocks are split
+// by the lists' lengths, which the rows of `ok` and the CSR's group sizes give without the lists;
+// every block then builds its own lists on its own device from the CSR and its rows of `ok`
+// (ca_estimate_plan_create_options).  The arguments were checked by the caller.
+static int multi_plan_from_options(ca_multi* mm, const ca_pod_table* t, const int32_t* eg_off, const int32_t* eg_pod,
+                                   int32_t n_eg, const uint8_t* ok, const ca_template* templates, int32_t n_groups,
+                                   int32_t* group_off_out, ca_multi_estimate_plan** out) {
+    // the row totals, on the replicas' host threads over an even row split
+    std::vector<int64_t> len((size_t)n_groups, 0);
+    const int32_t T = std::max(1, std::min((int32_t)mm->m.size(), n_groups));
+    const auto t0 = std::chrono::steady_clock::now();
+    if (n_eg > 0)
+        for_blocks(T, [&](int32_t k) {
+            const int32_t g0 = (int32_t)((int64_t)n_groups * k / T), g1 = (int32_t)((int64_t)n_groups * (k + 1) / T);
+            for (int32_t g = g0; g < g1; g++) {
+                const uint8_t* row = ok + (size_t)g * (size_t)n_eg;
+                int64_t c = 0;
+                for (int32_t e = 0; e < n_eg; e++) c += row[e] ? (int64_t)(eg_off[e + 1] - eg_off[e]) : 0;
+                len[g] = c;
+            }
+            return (int)CA_OK;
+        });
+    if (knob_env("CASIM_DEBUG_TIMING"))
+        fprintf(stderr, "[multi options] row totals %8.3f ms (%d x %d on %d threads)\n",
+                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), n_groups,
+                n_eg, T);
+    std::vector<int32_t> off((size_t)n_groups + 1, 0);
+    int64_t total = 0;
+    for (int32_t g = 0; g < n_groups; g++) {
+        total += len[g];
+        if (total > INT32_MAX) return CA_EINVAL;
+        off[(size_t)g + 1] = (int32_t)total;
+    }
+    auto* p = new ca_multi_estimate_plan();
+    p->mm = mm;
+    p->G = n_groups;
+    p->gb = split_blocks(n_groups, (int32_t)mm->m.size(), len);   // ca_multi_estimate_plan_create's blocks
+    p->off = std::move(off);
+    const int32_t D = (int32_t)p->gb.size() - 1;
+    p->ps.assign((size_t)D, nullptr);
+    p->pl.assign((size_t)D, nullptr);
+    const int rc = for_blocks(D, [&](int32_t d) {
+        const int32_t g0 = p->gb[d], g1 = p->gb[d + 1];
+        int r = ca_podset_create(mm->m[d], t, &p->ps[d]);
+        if (r != CA_OK) return r;
+        std::vector<int32_t> loff((size_t)(g1 - g0 + 1), 0);
+        r = ca_estimate_plan_create_options(mm->m[d], p->ps[d], eg_off, eg_pod, n_eg,
+                                            ok ? ok + (size_t)g0 * (size_t)n_eg : nullptr, templates + g0, g1 - g0,
+                                            loff.data(), &p->pl[d]);
+        if (r != CA_OK) return r;
+        for (int32_t g = g0; g <= g1; g++)
+            if (loff[g - g0] != p->off[g] - p->off[g0]) {
+                set_last_error("sharded plan from options: a block's list offsets differ from the row totals");
+                return (int)CA_EDEVICE;
+            }
+        return (int)CA_OK;
+    });
+    if (rc != CA_OK) { delete p; return rc; }
+    std::copy(p->off.begin(), p->off.end(), group_off_out);
+    *out = p;
+    return CA_OK;
+}
+
+int ca_multi_estimate_plan_create_options(ca_multi* mm, const ca_pod_table* t, const int32_t* eg_off,
+                                          const int32_t* eg_pod, int32_t n_eg, const uint8_t* ok,
+                                          const ca_template* templates, int32_t n_groups, int32_t* group_off_out,
+                                          ca_multi_estimate_plan** out) {
+    if (!mm || !t || t->n_pods < 0 || !eg_off || !out || !group_off_out || n_eg < 0 || n_groups < 0 ||
+        (n_groups > 0 && !templates) || (n_groups > 0 && n_eg > 0 && !ok))
+        return CA_EINVAL;
+    // ca_estimate_plan_create_options' checks, once for all blocks, before any of them allocates
+    if (eg_off[0] != 0) return CA_EINVAL;
+    for (int32_t e = 0; e < n_eg; e++)
+        if (eg_off[e + 1] < eg_off[e]) return CA_EINVAL;
+    if (eg_off[n_eg] > 0 && !eg_pod) return CA_EINVAL;
+    for (int32_t i = 0; i < eg_off[n_eg]; i++)
+        if ((uint32_t)eg_pod[i] >= (uint32_t)t->n_pods) return CA_EINVAL;
+    return multi_plan_from_options(mm, t, eg_off, eg_pod, n_eg, ok, templates, n_groups, group_off_out, out);
+}
+
+int ca_multi_estimate_plan_create_groups(ca_multi* mm, const ca_pod_table* t, const ca_pod_groups* g,
+                                         const uint8_t* ok, const ca_template* templates, int32_t n_groups,
+                                         int32_t* group_off_out, ca_multi_estimate_plan** out) {
+    if (!mm || !t || t->n_pods < 0 || !g || !g->s || !out || !group_off_out || n_groups < 0 ||
+        (n_groups > 0 && !templates) || (n_groups > 0 && g->n_eg > 0 && !ok))
+        return CA_EINVAL;
+    // the handle's CSR holds checked indices of its own pod set: they are t's when the sizes agree
+    if (g->s->n_host != t->n_pods) return CA_EINVAL;
+    return multi_plan_from_options(mm, t, g->h_eg_off.data(), g->h_eg_pod.data(), g->n_eg, ok, templates, n_groups,
+                                   group_off_out, out);
+}
+
+int ca_multi_estimate_plan_fetch_lists(const ca_multi_estimate_plan* p, int32_t* pod_idx, int32_t* item_cls) {
+    if (!p) return CA_EINVAL;
+    const int32_t D = (int32_t)p->gb.size() - 1;
+    return for_blocks(D, [&](int32_t d) {
+        const int32_t o = p->off[p->gb[d]];
+        return ca_estimate_plan_fetch_lists(p->pl[d], pod_idx ? pod_idx + o : nullptr, item_cls ? item_cls + o : nullptr);
+    });
+}
+
+int ca_multi_estimate_plan_lists_ms(const ca_multi_estimate_plan* p, float* ms, int32_t cap) {
+    if (!p || cap < 0 || (cap > 0 && !ms)) return CA_EINVAL;
+    const int32_t D = (int32_t)p->gb.size() - 1;
+    for (int32_t d = 0; d < D && d < cap; d++) {
+        float t[13] = {0};
+        ca_estimate_plan_timings(p->pl[d], t, 13);
+        ms[d] = t[12];
+    }
+    return D;
 }
 
 int ca_multi_estimate_plan_run(ca_multi_estimate_plan* p, const ca_limiter* limiter, int32_t* last_index,

@@ -153,6 +153,10 @@ def load() -> C.CDLL:
         "ca_multi_create": ([p(vp), i32, p(vp)], C.c_int),
         "ca_multi_destroy": ([vp], C.c_int),
         "ca_multi_estimate_plan_create": ([vp, vp, vp, vp, vp, i32, p(vp)], C.c_int),
+        "ca_multi_estimate_plan_create_options": ([vp, vp, vp, vp, i32, vp, vp, i32, vp, p(vp)], C.c_int),
+        "ca_multi_estimate_plan_create_groups": ([vp, vp, vp, vp, vp, i32, vp, p(vp)], C.c_int),
+        "ca_multi_estimate_plan_fetch_lists": ([vp, vp, vp], C.c_int),
+        "ca_multi_estimate_plan_lists_ms": ([vp, vp, i32], C.c_int),
         "ca_multi_estimate_plan_run": ([vp, vp, p(i32), vp, vp, vp], C.c_int),
         "ca_multi_estimate_plan_stats": ([vp, p(i32), p(i32), vp, i32], C.c_int),
         "ca_multi_estimate_plan_rerun_units": ([vp, p(i32)], C.c_int),
@@ -253,6 +257,8 @@ def exported_symbols() -> list[str]:
         "ca_multi_estimate_plan_fetch_group", "ca_multi_estimate_plan_fetch",
         "ca_multi_estimate_plan_groups_missing_pods", "ca_multi_estimate_plan_reader_ms",
         "ca_multi_estimate_plan_export_stats",
+        "ca_multi_estimate_plan_create_options", "ca_multi_estimate_plan_create_groups",
+        "ca_multi_estimate_plan_fetch_lists", "ca_multi_estimate_plan_lists_ms",
         "ca_multi_removal_plan_create", "ca_multi_removal_plan_run", "ca_multi_removal_plan_stats",
         "ca_multi_removal_plan_rerun_units", "ca_multi_removal_plan_timings",
         "ca_multi_removal_plan_destroy", "ca_multi_find_nodes_to_remove",
@@ -1418,17 +1424,75 @@ class MultiEstimatePlan:
         self.pod_idx = np.ascontiguousarray(pod_idx, dtype=np.int32)
         self.templates = np.ascontiguousarray(templates, dtype=abi.TEMPLATE_DTYPE)
         self.G = len(self.templates)
-        self.total = int(self.group_off[-1]) if len(self.group_off) else 0
         h = C.c_void_p()
         _check(self.lib.ca_multi_estimate_plan_create(multi.h, table.ref, ptr(self.group_off), ptr(self.pod_idx),
                                                       ptr(self.templates), self.G, C.byref(h)),
                "ca_multi_estimate_plan_create")
+        self._created(h)
+
+    def _created(self, h) -> None:
         self.h = h
+        self.total = int(self.group_off[-1]) if len(self.group_off) else 0
         n = max(self.total, 1)
         self._pinned = PinnedArray(self.lib, 2 * n, np.int32)
         self.sched_pod = self._pinned.array[:n]
         self.sched_node = self._pinned.array[n:]
         self.results = np.zeros(self.G, abi.ESTIMATE_RESULT_DTYPE)
+
+    @classmethod
+    def _options_plan(cls, multi: Multi, n_eg: int, ok, templates: np.ndarray) -> tuple:
+        """The fields every option-matrix plan starts from, and `ok` as [G * n_eg] uint8."""
+        self = cls.__new__(cls)
+        self.lib = multi.lib
+        self.h = None
+        self.templates = np.ascontiguousarray(templates, dtype=abi.TEMPLATE_DTYPE)
+        self.G = len(self.templates)
+        self.pod_idx = None
+        okm = np.ascontiguousarray(ok)
+        if okm.dtype != np.uint8:
+            okm = np.ascontiguousarray(okm != 0, dtype=np.uint8)
+        if okm.size != self.G * n_eg:
+            raise ValueError("ok: one verdict per (node group, pod equivalence group)")
+        self.group_off = np.zeros(self.G + 1, np.int32)
+        return self, okm
+
+    @classmethod
+    def from_options(cls, multi: Multi, table: abi.PodTable, eg_off, eg_pod, ok, templates: np.ndarray) -> "MultiEstimatePlan":
+        """EstimatePlan.from_options over the replicas (ca_multi_estimate_plan_create_options):
+        the blocks are split by the rows' totals, the split the list form takes from its
+        group_off, and every block builds its lists in its own device's memory from the CSR and
+        its own rows of `ok`.  `.group_off` comes from the library and `.pod_idx` is None
+        (fetch_lists() copies the lists out)."""
+        ego = np.ascontiguousarray(eg_off, dtype=np.int32)
+        egp = np.ascontiguousarray(eg_pod, dtype=np.int32)
+        if ego.ndim != 1 or len(ego) < 1:
+            raise ValueError("eg_off: n_eg + 1 offsets")
+        n_eg = len(ego) - 1
+        if len(egp) < int(ego[-1]):
+            raise ValueError("eg_pod is shorter than eg_off[-1]")
+        self, okm = cls._options_plan(multi, n_eg, ok, templates)
+        h = C.c_void_p()
+        _check(self.lib.ca_multi_estimate_plan_create_options(multi.h, table.ref, ptr(ego), ptr(egp), n_eg, ptr(okm),
+                                                              ptr(self.templates), self.G, ptr(self.group_off),
+                                                              C.byref(h)), "ca_multi_estimate_plan_create_options")
+        self._created(h)
+        return self
+
+    @classmethod
+    def from_groups(cls, multi: Multi, table: abi.PodTable, groups: "PodGroups", ok, templates: np.ndarray) -> "MultiEstimatePlan":
+        """from_options with the pod equivalence groups taken from a PodGroups handle
+        (ca_multi_estimate_plan_create_groups): the handle's host copy of its CSR is read, so it
+        may have been built on any mirror, over a pod set of `table`'s size.  The same plan as
+        from_options on groups.fetch()."""
+        if not isinstance(groups, PodGroups):
+            raise ValueError("from_groups: a PodGroups handle")
+        self, okm = cls._options_plan(multi, groups.n_groups, ok, templates)
+        h = C.c_void_p()
+        _check(self.lib.ca_multi_estimate_plan_create_groups(multi.h, table.ref, groups.h, ptr(okm), ptr(self.templates),
+                                                             self.G, ptr(self.group_off), C.byref(h)),
+               "ca_multi_estimate_plan_create_groups")
+        self._created(h)
+        return self
 
     READERS = {"sums": 0, "price": 1, "missing": 2}          # CA_MULTI_READER_*
 
@@ -1459,6 +1523,27 @@ class MultiEstimatePlan:
         self.lib.ca_multi_estimate_plan_rerun_units(self.h, C.byref(ru))
         return {"blocks": nb.value, "reruns": rr.value, "block_first_group": first[: nb.value + 1].tolist(),
                 "rerun_groups": ru.value}
+
+    def fetch_lists(self) -> tuple:
+        """The blocks' device lists in global group order (ca_multi_estimate_plan_fetch_lists;
+        plans of any constructor): (group_off, pod_idx [total], the score class of every item
+        [total], or None off the bucket path)."""
+        pod_idx = np.full(max(self.total, 1), -1, np.int32)
+        item_cls = np.full(max(self.total, 1), -1, np.int32)
+        _check(self.lib.ca_multi_estimate_plan_fetch_lists(self.h, ptr(pod_idx), ptr(item_cls)),
+               "ca_multi_estimate_plan_fetch_lists")
+        has_cls = self.total == 0 or bool((item_cls[: self.total] >= 0).all())
+        return self.group_off.copy(), pod_idx[: self.total], (item_cls[: self.total] if has_cls else None)
+
+    def lists_ms(self) -> np.ndarray:
+        """Per block, the device time (ms) of the kernels that built its lists from the option
+        matrix when the plan was created; 0 for a plan created from host lists."""
+        nb = C.c_int32(0)
+        _check(self.lib.ca_multi_estimate_plan_stats(self.h, C.byref(nb), None, None, 0),
+               "ca_multi_estimate_plan_stats")
+        ms = np.zeros(max(nb.value, 1), np.float32)
+        self.lib.ca_multi_estimate_plan_lists_ms(self.h, ptr(ms), nb.value)          # (returns the block count)
+        return ms[: nb.value]
 
     # The readers of EstimatePlan, same names and return shapes, over the blocks of the last
     # resident run (expander.DeviceOptions and nodegroupset.filter_plan_groups_by_pods take

@@ -326,8 +326,9 @@ def run(backend, util_fn, w: RunOnceWorkload, timers=None, row_zeros=_zeros, exp
     r.options = res.astype(np.uint8) if res.dtype == np.uint8 else (res["type"] == 0).astype(np.uint8)
 
     # 3. Estimate of every option, one batch.  A backend with estimate_options (the device
-    # mirror) gets the equivalence groups and the verdict matrix and builds the options' pod
-    # lists in its own memory; the others (the oracle, a sharded rank) get the lists.
+    # mirror, and a sharded rank for its own block of node groups) gets the equivalence groups
+    # and the verdict matrix and builds the options' pod lists in its own memory; the others
+    # (the oracle) get the lists.
     # (looked up on the class: a wrapper that forwards unknown attributes does not count)
     if pg is not None:
         t = clock()
@@ -432,8 +433,41 @@ class ShardedMirror:
     def __getattr__(self, k):                     # podset, filter_out_schedulable, h, lib, ...
         return getattr(self.m, k)
 
+    def build_pod_groups(self, podset, order=None, node=None, class_owner=None):
+        """Mirror.build_pod_groups on this rank's replica: every rank applied
+        FilterOutSchedulable itself, so every rank builds the same groups."""
+        return self.m.build_pod_groups(podset, order=order, node=node, class_owner=class_owner)
+
+    def estimate_options(self, table_or_podset, eg_off, eg_pod, ok, templates, max_nodes, last_index=0,
+                         want_nodes=False, groups=None):
+        """Mirror.estimate_options with the node groups sharded: the blocks come from the option
+        matrix (shard.option_blocks, the split of the lists' lengths), and this rank builds the
+        lists of its own rows `ok[a:b]` in its replica's memory (EstimatePlan.from_options, or
+        .from_groups with `groups`, a PodGroups on this replica: the totals then come from
+        groups.fetch()).  Returns (EstimateOutput of the whole batch, group_off)."""
+        from . import native, shard
+        if want_nodes:
+            raise NotImplementedError("ShardedMirror.estimate_options: sched_node is not gathered across ranks")
+        ego = groups.fetch()[0] if groups is not None else np.ascontiguousarray(eg_off, np.int32)
+        tm = np.ascontiguousarray(templates, dtype=abi.TEMPLATE_DTYPE)
+        okm = np.ascontiguousarray(ok).reshape(len(tm), len(ego) - 1)
+        off, blocks = shard.option_blocks(ego, okm, self.world)
+        a, b = blocks[self.rank], blocks[self.rank + 1]
+        if groups is not None:
+            plan = native.EstimatePlan.from_groups(self.m, table_or_podset, groups, okm[a:b], tm[a:b])
+        else:
+            plan = native.EstimatePlan.from_options(self.m, table_or_podset, ego, eg_pod, okm[a:b], tm[a:b])
+        with plan:
+            if not np.array_equal(plan.group_off, off[a:b + 1] - off[a]):
+                raise RuntimeError("ShardedMirror.estimate_options: the block's offsets differ from the row totals")
+            res, sched, L, reruns = shard.estimate_sharded(plan, max_nodes, last_index, self.ex, self.rank, blocks, off)
+        self.stats["estimate_reruns"] = reruns
+        return native.EstimateOutput(res, sched, None, L), off
+
     def estimate(self, table, group_off, pod_idx, templates, max_nodes, last_index=0, want_nodes=False, podset=None):
         from . import native, shard
+        if want_nodes:
+            raise NotImplementedError("ShardedMirror.estimate: sched_node is not gathered across ranks")
         off = np.ascontiguousarray(group_off, np.int32)
         blocks = shard.split_blocks(np.diff(off), self.world)
         a, b = blocks[self.rank], blocks[self.rank + 1]

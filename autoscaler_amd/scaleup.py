@@ -129,10 +129,10 @@ def BuildPodGroupsOnDevice(snapshot: ClusterSnapshot, pods: list) -> DevicePodGr
     return out
 
 
-def _device_groups(pod_groups, option_lists: str, multi):
+def _device_groups(pod_groups, option_lists: str):
     """The DevicePodGroups whose handle the facades read: given as the pod groups, with the
-    lists built on the device and one mirror."""
-    return pod_groups if isinstance(pod_groups, DevicePodGroups) and option_lists == "device" and multi is None else None
+    lists built on the device."""
+    return pod_groups if isinstance(pod_groups, DevicePodGroups) and option_lists == "device" else None
 
 
 @dataclass
@@ -201,7 +201,9 @@ def _resident_estimate(snapshot: ClusterSnapshot, checker: SchedulerBasedPredica
     `options` = (eg_off, eg_pod, ok) (see _option_inputs) the plan builds the lists itself
     (native.EstimatePlan.from_options) and pod_idx / offs are not read.  With `device_groups` (a
     DevicePodGroups; all_pods is then its pods in input order and options[2] the matrix over all
-    of its groups) the plan reads the groups from the handle (native.EstimatePlan.from_groups)."""
+    of its groups) the plan reads the groups from the handle (native.EstimatePlan.from_groups).
+    With `multi` both forms build the sharded plan's counterpart (MultiEstimatePlan.from_options /
+    .from_groups, the handle resident on the snapshot's backend): every block builds its own lists."""
     from . import native
     from .expander import DeviceOptions, resources_for_node
     from .predicatechecker import unsupported
@@ -213,17 +215,24 @@ def _resident_estimate(snapshot: ClusterSnapshot, checker: SchedulerBasedPredica
         templates[g] = snapshot.interner.encode_template(info.node, list(info.pods))
     caps = [resources_for_node(info.node) for _, info in est_groups]
     with unsupported("Estimate: the snapshot holds a pod with required anti-affinity"):
+        if multi is not None:
+            for m in multi.mirrors:            # (after _feasible_pods, which may have re-interned and replayed)
+                snapshot.sync_replica(m)
         if device_groups is not None:
             ps, handle = device_groups.resident(snapshot, table)
-            plan = native.EstimatePlan.from_groups(snapshot.backend, ps, handle, options[2], templates)
+            if multi is None:
+                plan = native.EstimatePlan.from_groups(snapshot.backend, ps, handle, options[2], templates)
+            else:
+                plan = native.MultiEstimatePlan.from_groups(multi, table, handle, options[2], templates)
         elif options is not None:
-            plan = native.EstimatePlan.from_options(snapshot.backend, table, *options, templates)
+            if multi is None:
+                plan = native.EstimatePlan.from_options(snapshot.backend, table, *options, templates)
+            else:
+                plan = native.MultiEstimatePlan.from_options(multi, table, *options, templates)
         elif multi is None:
             plan = native.EstimatePlan(snapshot.backend, table, np.array(offs, np.int32),
                                        np.array(pod_idx, np.int32), templates)
         else:
-            for m in multi.mirrors:            # (after _feasible_pods, which may have re-interned and replayed)
-                snapshot.sync_replica(m)
             plan = native.MultiEstimatePlan(multi, table, np.array(offs, np.int32), np.array(pod_idx, np.int32),
                                             templates)
     node_infos = {(ng.Id() if hasattr(ng, "Id") else ng): info for ng, info in node_groups}
@@ -271,8 +280,11 @@ def _handle_inputs(dpg: DevicePodGroups, est_index: list, feas):
     return dpg.pods, (None, None, np.ascontiguousarray(ok, np.uint8))
 
 
-def _check_option_lists(option_lists) -> str:
-    option_lists = OPTION_LISTS_DEFAULT if option_lists is None else option_lists
+def _check_option_lists(option_lists, multi=None) -> str:
+    """`option_lists` with its default filled in: OPTION_LISTS_DEFAULT on one mirror, "host" with
+    `multi` (the sharded default waits for a measurement on several physical devices)."""
+    if option_lists is None:
+        option_lists = OPTION_LISTS_DEFAULT if multi is None else "host"
     if option_lists not in ("device", "host"):
         raise ValueError('option_lists: "device" or "host"')
     return option_lists
@@ -300,18 +312,18 @@ def ComputeBestExpansionOption(snapshot: ClusterSnapshot, checker: SchedulerBase
     everything after the run is the same code.  `option_lists`: "host" appends the options' pod
     lists here and uploads them; "device" encodes every pod of a passing pod group once and
     hands the pod groups and the feasibility matrix to the plan, which builds the lists in
-    device memory (same results).  With `multi` the host lists stay: the sharded plan takes
-    lists only."""
+    device memory (same results); with `multi` every block builds the lists of its own node
+    groups on its own device.  None: "device" on one mirror, "host" with `multi`."""
     _backend_must_be_mirror(snapshot, "ComputeBestExpansionOption")
-    option_lists = _check_option_lists(option_lists)
+    option_lists = _check_option_lists(option_lists, multi)
     est_groups, est_index, feas = _feasible_pods(snapshot, pod_groups, node_groups)
     if not est_groups:
         return None, feas
     all_pods, offs, options = [], [0], None
-    dpg = _device_groups(pod_groups, option_lists, multi)
+    dpg = _device_groups(pod_groups, option_lists)
     if dpg is not None:
         all_pods, options = _handle_inputs(dpg, est_index, feas)
-    elif option_lists == "device" and multi is None:
+    elif option_lists == "device":
         all_pods, options = _option_inputs(pod_groups, est_index, feas)
     else:
         for pods, _ in est_groups:
@@ -351,21 +363,20 @@ def ComputeBalancedScaleUp(snapshot: ClusterSnapshot, checker: SchedulerBasedPre
     ComputeBestExpansionOption; the winner's list then crosses devices only if a similar group's
     option lies in another block (casim.h, ca_multi_estimate_plan_groups_missing_pods).
     `option_lists`: as on ComputeBestExpansionOption ("device": the pod_idx slices are built in
-    device memory from the pod groups and the feasibility matrix; with `multi` the host lists
-    stay, the sharded plan takes lists only)."""
+    device memory from the pod groups and the feasibility matrix)."""
     from .nodegroupset import filter_plan_groups_by_pods
 
     _backend_must_be_mirror(snapshot, "ComputeBalancedScaleUp")
-    option_lists = _check_option_lists(option_lists)
+    option_lists = _check_option_lists(option_lists, multi)
     est_groups, est_index, feas = _feasible_pods(snapshot, pod_groups, node_groups)
     if not est_groups:
         return None, [], feas
     all_pods, row = [], {}
     pod_idx, offs, options = [], [0], None
-    dpg = _device_groups(pod_groups, option_lists, multi)
+    dpg = _device_groups(pod_groups, option_lists)
     if dpg is not None:
         all_pods, options = _handle_inputs(dpg, est_index, feas)
-    elif option_lists == "device" and multi is None:
+    elif option_lists == "device":
         all_pods, options = _option_inputs(pod_groups, est_index, feas)
     else:
         for pods, _ in est_groups:                  # the shared table: every feasible pod once

@@ -95,6 +95,25 @@ def split_blocks(weights, world: int) -> list:
     return b
 
 
+def option_blocks(eg_off, ok, world: int) -> tuple:
+    """The blocks of an Estimate batch given as its option matrix (`ok` [G][E]: pod equivalence
+    group e, of eg_off[e + 1] - eg_off[e] pods, passes on node group g), without its lists: row
+    g's total is the length of group g's list, so the prefix sums are the lists' group_off and
+    split_blocks of the totals the blocks of the list form.  The split
+    ca_multi_estimate_plan_create_options makes.  Returns (group_off int32 [G + 1], blocks)."""
+    import numpy as np
+    sizes = np.diff(np.ascontiguousarray(eg_off, dtype=np.int64))
+    okm = np.asarray(ok)
+    if okm.ndim != 2:                          # a flat matrix: rows of n_eg verdicts (none when n_eg == 0)
+        okm = okm.reshape(-1, len(sizes)) if len(sizes) else okm.reshape(0, 0)
+    totals = (okm != 0).astype(np.int64) @ sizes
+    if int(totals.sum()) > np.iinfo(np.int32).max:
+        raise ValueError("option_blocks: the lists' total does not fit int32")
+    group_off = np.zeros(len(totals) + 1, np.int32)
+    np.cumsum(totals, out=group_off[1:])
+    return group_off, split_blocks(totals, world)
+
+
 def torch_gather_bytes(dist, device) -> Callable:
     """all_gather of an equal-sized numpy array per rank (any dtype, moved as bytes) over
     torch.distributed (RCCL over xGMI, or gloo): returns every rank's array, in rank order."""

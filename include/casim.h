@@ -870,6 +870,39 @@ typedef struct ca_multi_estimate_plan ca_multi_estimate_plan;
 int ca_multi_estimate_plan_create(ca_multi* mm, const ca_pod_table* t, const int32_t* group_off,
                                   const int32_t* pod_idx, const ca_template* templates, int32_t n_groups,
                                   ca_multi_estimate_plan** out);
+/* The same plan from the option matrix, as ca_estimate_plan_create_options builds the one-device
+ * plan: eg_off / eg_pod / n_eg / ok / templates / group_off_out mean what they mean there, t is
+ * the pod table as on ca_multi_estimate_plan_create (eg_pod holds indices into it).  The row
+ * totals len[g] = sum over e with ok[g*n_eg+e] != 0 of eg_off[e+1] - eg_off[e] (one pass over ok
+ * on the replicas' host threads) give group_off_out and the blocks: the same split by the same
+ * weights as ca_multi_estimate_plan_create takes from group_off, so this plan and the plan made
+ * from the lists the options denote have the same blocks.  Every block then builds its lists on
+ * its own device with ca_estimate_plan_create_options over its rows of ok: a device receives the
+ * CSR (4 B per offset and per pod) and its own rows of ok, not 4 B per item.  Everything after
+ * creation (run, the readers, stats) is that of ca_multi_estimate_plan_create's plan.
+ * CA_EINVAL, before any launch or allocation on any device and with *out untouched: every cause
+ * of ca_estimate_plan_create_options (eg_off[0] != 0 or eg_off decreasing, an eg_pod entry outside
+ * the table, a total that does not fit int32); mm, t, out or group_off_out NULL; n_groups > 0
+ * without templates.  A failure inside one block destroys what the other blocks created. */
+int ca_multi_estimate_plan_create_options(ca_multi* mm, const ca_pod_table* t, const int32_t* eg_off,
+                                          const int32_t* eg_pod, int32_t n_eg, const uint8_t* ok,
+                                          const ca_template* templates, int32_t n_groups,
+                                          int32_t* group_off_out, ca_multi_estimate_plan** out);
+/* ca_multi_estimate_plan_create_options with eg_off / eg_pod / n_eg taken from the handle's host
+ * copy of its CSR.  g may have been built on any mirror (typically the replica that ran
+ * FilterOutSchedulable) and the pod set it was built on must still exist; its device copy is not
+ * used, a block's pod set is the plan's own.  CA_EINVAL in addition: g's pod set and t differ in
+ * size. */
+int ca_multi_estimate_plan_create_groups(ca_multi* mm, const ca_pod_table* t, const ca_pod_groups* g,
+                                         const uint8_t* ok, const ca_template* templates, int32_t n_groups,
+                                         int32_t* group_off_out, ca_multi_estimate_plan** out);
+/* The blocks' ca_estimate_plan_fetch_lists concatenated in global group order (plans of any
+ * constructor; for tests and Go-side checks).  Either pointer may be NULL; item_cls as there. */
+int ca_multi_estimate_plan_fetch_lists(const ca_multi_estimate_plan* p, int32_t* pod_idx, int32_t* item_cls);
+/* Per block, the device time (ms) of the kernels that built its lists from the option matrix
+ * (the block plan's ca_estimate_plan_timings[12]; 0 for a plan created from host lists).  Writes
+ * min(cap, blocks) values and returns the block count. */
+int ca_multi_estimate_plan_lists_ms(const ca_multi_estimate_plan* p, float* ms, int32_t cap);
 int ca_multi_estimate_plan_run(ca_multi_estimate_plan* p, const ca_limiter* limiter, int32_t* last_index,
                                ca_estimate_result* results, int32_t* sched_pod, int32_t* sched_node);
 /* sched_pod == NULL (and sched_node == NULL; sched_node without sched_pod is CA_EINVAL) is a
