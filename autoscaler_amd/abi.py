@@ -153,6 +153,37 @@ UTIL_INFO_DTYPE = np.dtype([
 ], align=True)
 
 
+# ca_scale_down_candidates node classes (include/casim.h CA_SD_*)
+CA_SD_NOT_BELOW, CA_SD_EMPTY, CA_SD_CANDIDATE, CA_SD_UTIL_ERROR, CA_SD_INELIGIBLE = 0, 1, 2, 3, 4
+
+
+class MirrorUtilArgsC(C.Structure):
+    """ca_mirror_util_args (not in ca_abi_struct_sizes: that list is frozen at ABI version 3)."""
+    _fields_ = [("skip_daemonset_pods", C.c_int32), ("skip_mirror_pods", C.c_int32), ("now_ns", C.c_int64),
+                ("node_pos", C.c_void_p), ("node_rows", C.c_void_p), ("n_node_rows", C.c_int32),
+                ("pod_ids", C.c_void_p), ("pod_rows", C.c_void_p), ("n_pod_rows", C.c_int32)]
+
+
+def mirror_util_args(skip_ds, skip_mirror, now_ns: int, node_over=None, pod_over=None):
+    """(MirrorUtilArgsC, the arrays it points into).  node_over = (positions, UTIL_NODE rows) and
+    pod_over = (mirror pod ids, UTIL_POD rows), or None."""
+    keep = []
+    a = MirrorUtilArgsC(int(bool(skip_ds)), int(bool(skip_mirror)), int(now_ns), None, None, 0, None, None, 0)
+    for over, dt, names in ((node_over, UTIL_NODE_DTYPE, ("node_pos", "node_rows", "n_node_rows")),
+                            (pod_over, UTIL_POD_DTYPE, ("pod_ids", "pod_rows", "n_pod_rows"))):
+        if over is None:
+            continue
+        ids = np.ascontiguousarray(over[0], dtype=np.int32)
+        rows = np.ascontiguousarray(over[1], dtype=dt) if over[1] is not None else None
+        if rows is not None and len(rows) != len(ids):
+            raise ValueError("override ids and rows differ in length")
+        keep += [ids, rows]
+        setattr(a, names[0], ptr(ids))
+        setattr(a, names[1], ptr(rows))
+        setattr(a, names[2], len(ids))
+    return a, keep
+
+
 class PodTableC(C.Structure):
     _fields_ = [
         ("pods", C.c_void_p), ("n_pods", C.c_int32), ("n_terms", C.c_int32),

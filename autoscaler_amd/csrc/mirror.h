@@ -111,6 +111,22 @@ struct PlanChainScratch {
     HostBuf h_in, h_out;
 };
 
+// Per-mirror scratch of ca_mirror_utilization / ca_scale_down_candidates_create (scaledown.hip),
+// kept across calls.
+struct UtilScratch {
+    DevBuf in;                     // one call's inputs: [pod -> node | node rows | override ids, rows, bitmap | eligible]
+    HostBuf h_in;                  // ... staged in page-locked memory, one H2D copy per call
+    DevBuf acc;                    // per-node sums (util_core.h UtilSum): all zero between calls
+    size_t acc_rows = 0;           // rows of acc that exist and are zero
+    bool acc_dirty = false;        // a call ended without its node kernel clearing acc: zero it first
+    DevBuf info, drain;            // the last call's ca_util_info rows and drain bits, [n_nodes]
+    DevBuf cls;                    // ca_scale_down_candidates_create: [counts | empty | cand | status | class]
+    HostBuf h_cls;
+    int32_t n_nodes = 0;           // rows valid in info / drain
+    float stage_ms = 0;            // host time of the last call's pod -> node staging fill
+    int64_t h2d_bytes = 0, d2h_bytes = 0;   // bytes the last call moved across PCIe
+};
+
 // Dirty-row staging of sync_nodes: one H2D copy + a scatter kernel.
 struct RowStage {
     DevBuf d;
@@ -290,6 +306,7 @@ struct ca_mirror {
     casim::FilterScratch fo;
     casim::PlanChainScratch pc;
     casim::RowStage rs;
+    casim::UtilScratch ut;
     casim::HostBuf podset_stage;           // ca_podset_create: the records' page-locked staging
     // resident HintingSimulator hints (hints.go:29-72): node per mirror pod, -1 = none
     casim::DevBuf d_pod_hints;

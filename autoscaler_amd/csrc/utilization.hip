@@ -14,6 +14,7 @@
 // node and writes its 48 B Info row.  16 nodes per 256-thread workgroup; 15 000 nodes
 // (C5) launch 938 workgroups, 3 750 wavefronts: one resident round on 256 CUs.
 #include "casim_internal.h"
+#include "util_core.h"
 
 #include <algorithm>
 #include <cstring>
@@ -43,42 +44,17 @@ namespace {
 inline size_t added_pods_at(int32_t n) { return ((sizeof(int32_t) * (size_t)std::max(n, 1)) + 63) & ~(size_t)63; }
 
 // the added pods' sums of one node (k_added_sums), consumed and cleared by k_node_utilization
-struct AddedSum {
-    unsigned long long req[3], dsm[3];       // int64 sums (two's complement adds)
-    int32_t drain, pad;
-    int64_t pad2;
-};
-static_assert(sizeof(AddedSum) == 64, "AddedSum");
+using AddedSum = casim::UtilSum;
+using casim::node_info;
+using casim::pod_share;
+using casim::util_sum_add;
 
 constexpr int kLanes = 16;                                    // lanes per node (C5: ~20 pods/node)
 constexpr int kThreads = 256;
-constexpr int64_t kNsPerS = 1000000000LL;
-constexpr int64_t kLongTerminatingExtraNs = 30 * kNsPerS;   // drain.go:34 PodLongTerminatingExtraThreshold
-
-// calculateUtilizationOfResource's final ratio (info.go:126): float64 / float64 of the
-// MilliValue difference, one correctly rounded IEEE division (built -ffp-contract=off).
-__device__ inline double util_ratio(int64_t pods, int64_t alloc, int64_t dsm) {
-    return (double)pods / (double)(alloc - dsm);
-}
 
 __device__ inline int64_t seg_sum(int64_t v) {                // within a kLanes-lane segment
     for (int o = kLanes / 2; o; o >>= 1) v += __shfl_xor(v, o, kLanes);
     return v;
-}
-
-// one pod's share of its node's sums (info.go:100-124)
-__device__ inline void pod_share(const ca_util_pod& p, int32_t skip_ds, int32_t skip_mirror, int64_t now_ns,
-                                 int64_t (&req)[3], int64_t (&dsm)[3], int& drain) {
-    drain |= (int)(p.flags & (CA_UPOD_MOVABLE | CA_UPOD_BLOCKING));
-    const bool factored = (skip_ds && (p.flags & CA_UPOD_DAEMONSET)) || (skip_mirror && (p.flags & CA_UPOD_MIRROR));
-    // drain.IsPodLongTerminating (utils/drain/drain.go:294-306): deleted, and deletion +
-    // grace + 30 s strictly before now
-    const bool long_term = !factored && (p.flags & CA_UPOD_DELETED) &&
-                           p.deletion_ns + p.grace_s * kNsPerS + kLongTerminatingExtraNs < now_ns;
-    for (int r = 0; r < 3; r++) {
-        if (factored) dsm[r] += p.req_milli[r];
-        else if (!long_term) req[r] += p.req_milli[r];
-    }
 }
 
 // The pods added since the rows were set, one thread each, into their nodes' sums
@@ -93,12 +69,7 @@ __global__ __launch_bounds__(kThreads) void k_added_sums(const int32_t* __restri
     int64_t req[3] = {0, 0, 0}, dsm[3] = {0, 0, 0};
     int drain = 0;
     pod_share(add_pods[k], skip_ds, skip_mirror, now_ns, req, dsm, drain);
-    AddedSum& a = acc[x];
-    for (int r = 0; r < 3; r++) {
-        if (req[r]) atomicAdd(&a.req[r], (unsigned long long)req[r]);
-        if (dsm[r]) atomicAdd(&a.dsm[r], (unsigned long long)dsm[r]);
-    }
-    if (drain) atomicOr(&a.drain, drain);
+    util_sum_add(acc[x], req, dsm, drain);
 }
 
 __global__ __launch_bounds__(kThreads) void k_node_utilization(
@@ -127,32 +98,7 @@ __global__ __launch_bounds__(kThreads) void k_node_utilization(
         if (a.drain | a.req[0] | a.req[1] | a.req[2] | a.dsm[0] | a.dsm[1] | a.dsm[2]) acc[node] = AddedSum{};
     }
 
-    ca_util_info o;
-    o.cpu = o.mem = o.gpu = o.utilization = 0.0;
-    o.resource = CA_UTIL_CPU;
-    o.status = CA_UTIL_OK;
-    o._pad = 0;
-    o.empty = drain == 0;                                         // cluster.go:197-199
-    if (nd.flags & CA_UNODE_GPU_CONFIG) {                         // info.go:49-58
-        o.resource = CA_UTIL_GPU;
-        if ((nd.flags & CA_UNODE_HAS_GPU) && nd.alloc_milli[2] != 0) {
-            o.gpu = util_ratio(req[2], nd.alloc_milli[2], dsm[2]);
-            o.utilization = o.gpu;
-        }                                                         // unready GPU: Info{Gpu 0, Util 0}, nil
-    } else if (!(nd.flags & CA_UNODE_HAS_CPU)) {                  // info.go:88-94 -> Info{}, err
-        o.status = CA_UTIL_NO_CPU;
-    } else if (nd.alloc_milli[0] == 0) {
-        o.status = CA_UTIL_ZERO_CPU;
-    } else if (!(nd.flags & CA_UNODE_HAS_MEM)) {
-        o.status = CA_UTIL_NO_MEM;
-    } else if (nd.alloc_milli[1] == 0) {
-        o.status = CA_UTIL_ZERO_MEM;
-    } else {                                                      // info.go:61-80
-        o.cpu = util_ratio(req[0], nd.alloc_milli[0], dsm[0]);
-        o.mem = util_ratio(req[1], nd.alloc_milli[1], dsm[1]);
-        if (o.cpu > o.mem) { o.resource = CA_UTIL_CPU; o.utilization = o.cpu; }
-        else               { o.resource = CA_UTIL_MEM; o.utilization = o.mem; }
-    }
+    const ca_util_info o = node_info(nd, req, dsm, drain);
     out[node] = o;
     if (out_host) out_host[node] = o;                             // page-locked caller rows (zero-copy)
 }

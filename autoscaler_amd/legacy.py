@@ -121,7 +121,13 @@ class ScaleDown:
 
     def __init__(self, snapshot: ClusterSnapshot, removal_simulator: sim.RemovalSimulator, node_groups: dict,
                  options: ScaleDownOptions, gpu_configs: Optional[dict] = None,
-                 calculate_all: Optional[Callable] = None):
+                 calculate_all: Optional[Callable] = None, device_candidates: bool = False):
+        if device_candidates:
+            from .native import Mirror
+            if not isinstance(snapshot.backend, Mirror):
+                raise TypeError("device_candidates=True needs the device mirror as the snapshot's backend")
+        self.device_candidates = device_candidates
+        self.device_updates = 0                        # UpdateUnneededNodes calls served by the candidates handle
         self.snapshot = snapshot
         self.removal_simulator = removal_simulator
         self.node_groups = node_groups                 # node name -> NodeGroup (NodeGroupForNode)
@@ -181,7 +187,9 @@ class ScaleDown:
 
     # getEmptyNodesToRemove (legacy.go:364-422) without resource limits
     def _empty_nodes_to_remove(self, candidates: list, timestamp: float) -> list:
-        empty = self.removal_simulator.FindEmptyNodesToRemove(candidates, timestamp)
+        return self._empty_within_limits(self.removal_simulator.FindEmptyNodesToRemove(candidates, timestamp))
+
+    def _empty_within_limits(self, empty: list) -> list:
         available: dict = {}
         out = []
         for name in empty:
@@ -203,28 +211,121 @@ class ScaleDown:
         non = [n for n in nodes if not self.unneeded_nodes.Contains(n)]
         return cand, non
 
+    def _host_reason(self, node: Node, names: set, timestamp: float) -> int:
+        """The checks of FilterOutUnremovable that need no utilization, in its order
+        (eligibility.go:66-147); NoReason: the node goes on to the threshold check."""
+        if node.name not in names:
+            return sim.UnexpectedError
+        if self.unremovable_nodes.IsRecent(node.name):
+            return sim.RecentlyUnremovable
+        if is_node_being_deleted(node, timestamp):
+            return sim.CurrentlyBeingDeleted
+        if node.annotations.get(ScaleDownDisabledKey) == "true":
+            return sim.ScaleDownDisabledAnnotation
+        if self.node_groups.get(node.name) is None:
+            return sim.NotAutoscaled
+        if not self.options.scale_down_unready_enabled and not node.ready:
+            return sim.ScaleDownUnreadyDisabled
+        return sim.NoReason
+
+    def _device_inputs(self, dest: list, scale_down_candidates: list, timestamp: float):
+        """FilterOutUnremovable, the empty nodes and the sweeps' inputs from one
+        native.ScaleDownCandidates on the snapshot's mirror: the host's eligibility checks go in
+        as the `eligible` mask, its GetPodsToMove verdicts as pod override rows.  Returns
+        (unneeded, util_map, ineligible, empty, sweep), `sweep(names)` standing in for
+        FindNodesToRemove, or None when a host verdict has no form in the handle (a drain error
+        without a blocking pod, a utilization error, a candidate that is no destination, an empty
+        node beyond its group's limits): the caller then takes the host path.  Changes nothing
+        before it returns."""
+        import numpy as np
+        from . import abi
+        from .drain import get_pods_to_move
+        snap, rs, opt = self.snapshot, self.removal_simulator, self.options
+        names = snap.node_names()
+        in_snap, dest_set = set(names), set(dest)
+        reasons = {n.name: self._host_reason(n, in_snap, timestamp) for n in scale_down_candidates}
+        eligible = np.zeros(len(names), np.uint8)
+        verdicts, flag = {}, {}
+        for name, reason in reasons.items():
+            if reason != sim.NoReason:
+                continue
+            if name not in dest_set:
+                return None
+            eligible[snap.position(name)] = 1
+            v = get_pods_to_move(snap.Get(name).pods, rs.delete_options, rs.listers, [], timestamp)
+            if v[3] is not None and v[2] is None:
+                return None
+            verdicts[name] = v
+            if v[3] is None:
+                flag.update((id(p), abi.CA_UPOD_MOVABLE) for p in v[0])
+            else:
+                flag[id(v[2].pod)] = abi.CA_UPOD_BLOCKING
+        node_over, pod_over = utilization.snapshot_overrides(snap, list(verdicts), self.gpu_configs,
+                                                             pod_flags=lambda p: flag.get(id(p), 0))
+        sd = snap.backend.scale_down_candidates(
+            opt.ignore_daemonsets_utilization, opt.ignore_mirror_pods_utilization, round(timestamp * 1e9),
+            opt.scale_down_utilization_threshold, opt.scale_down_gpu_utilization_threshold, eligible, node_over, pod_over)
+        ls = sd.fetch()
+        if (ls.node_class == abi.CA_SD_UTIL_ERROR).any():
+            sd.close()
+            return None
+        unneeded, util_map, ineligible, empty = [], {}, [], []
+        for node in scale_down_candidates:
+            if reasons[node.name] != sim.NoReason:
+                ineligible.append(sim.UnremovableNode(node, reasons[node.name]))
+                continue
+            pos = snap.position(node.name)
+            util_map[node.name] = utilization.info_from_row(ls.info[pos], node.name, self.gpu_configs.get(node.name))[0]
+            if ls.node_class[pos] == abi.CA_SD_NOT_BELOW:
+                ineligible.append(sim.UnremovableNode(node, sim.NotUnderutilized))
+                continue
+            unneeded.append(node.name)
+            if ls.node_class[pos] == abi.CA_SD_EMPTY:
+                empty.append(node.name)
+        within = self._empty_within_limits(empty)
+        if len(within) != len(empty):
+            sd.close()
+            return None
+        mask = np.array([n in dest_set for n in names], np.uint8)
+
+        def sweep(cands: list):
+            if not cands:
+                return [], []
+            with sd.removal_plan(nodes=[snap.position(n) for n in cands], dest_mask=mask) as plan:
+                return rs.FindNodesToRemovePlanned(plan, cands, verdicts)
+        sweep.close = sd.close
+        return unneeded, util_map, ineligible, within, sweep
+
     def UpdateUnneededNodes(self, destination_nodes: list, scale_down_candidates: list,  # noqa: N802
                             timestamp: float) -> None:
         """legacy.go:101-225."""
         all_nodes = self.snapshot.node_names()
         self.unremovable_nodes.Update(self.snapshot, timestamp)
-        unneeded, util_map, ineligible = self._filter_out_unremovable(scale_down_candidates, timestamp)
+        dest = [n.name for n in destination_nodes]
+        dev = self._device_inputs(dest, scale_down_candidates, timestamp) if self.device_candidates else None
+        if dev is not None:
+            unneeded, util_map, ineligible, empty, sweep = dev
+            self.device_updates += 1
+        else:
+            unneeded, util_map, ineligible = self._filter_out_unremovable(scale_down_candidates, timestamp)
+            empty = self._empty_nodes_to_remove(unneeded, timestamp)
+            sweep = lambda names: self.removal_simulator.FindNodesToRemove(names, dest, timestamp, [])  # noqa: E731
         for u in ineligible:
             self.unremovable_nodes.Add(u)
-        empty = self._empty_nodes_to_remove(unneeded, timestamp)
         empty_names = {e.node.name for e in empty}
         non_empty = [n for n in unneeded if n not in empty_names]
         cand, non = self._choose_candidates(non_empty)
-        dest = [n.name for n in destination_nodes]
-        to_remove, unremovable = self.removal_simulator.FindNodesToRemove(cand, dest, timestamp, [])
+        to_remove, unremovable = sweep(cand)
         extra = self.options.scale_down_non_empty_candidates_count - len(to_remove)
         extra = min(extra, len(non))
         pool = int(math.ceil(len(all_nodes) * self.options.scale_down_candidates_pool_ratio))
         pool = min(max(pool, self.options.scale_down_candidates_pool_min_count), len(non))
         if extra > 0:
-            more, more_un = self.removal_simulator.FindNodesToRemove(non[:pool], dest, timestamp, [])
+            more, more_un = sweep(non[:pool])
             to_remove += more[:extra]
             unremovable += more_un
+        if dev is not None:
+            sweep.close()
         to_remove += empty
         self.unneeded_nodes.Update(to_remove, timestamp)
         if unremovable:

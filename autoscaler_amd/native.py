@@ -150,6 +150,13 @@ def load() -> C.CDLL:
         "ca_util_table_set_added": ([vp, vp, vp, i32], C.c_int),
         "ca_util_calculate": ([vp, i32, i32, C.c_int64, vp, p(C.c_float)], C.c_int),
         "ca_util_device_results": ([vp, p(vp)], C.c_int),
+        "ca_mirror_utilization": ([vp, vp, vp, vp, p(C.c_float)], C.c_int),
+        "ca_scale_down_candidates_create": ([vp, vp, C.c_double, C.c_double, vp, p(vp)], C.c_int),
+        "ca_scale_down_candidates_info": ([vp, p(i32), p(i32), p(i32), p(i32)], C.c_int),
+        "ca_scale_down_candidates_fetch": ([vp, vp, vp, vp, vp, vp, vp, vp], C.c_int),
+        "ca_scale_down_candidates_timings": ([vp, p(C.c_float), i32], C.c_int),
+        "ca_scale_down_candidates_destroy": ([vp], C.c_int),
+        "ca_removal_plan_create_candidates": ([vp, vp, i32, vp, p(vp)], C.c_int),
         "ca_multi_create": ([p(vp), i32, p(vp)], C.c_int),
         "ca_multi_destroy": ([vp], C.c_int),
         "ca_multi_estimate_plan_create": ([vp, vp, vp, vp, vp, i32, p(vp)], C.c_int),
@@ -250,7 +257,10 @@ def exported_symbols() -> list[str]:
         "ca_mirror_sync_stats", "ca_mirror_reorder_nodes", "ca_mirror_reorder_stats", "ca_multi_reorder_nodes",
         "ca_removal_candidate_ticks", "ca_filter_out_schedulable", "ca_try_schedule_pods", "ca_filter_stats",
         "ca_util_table_create", "ca_util_table_destroy", "ca_util_calculate", "ca_util_device_results",
-        "ca_util_table_update", "ca_util_table_set_added", "ca_multi_create", "ca_multi_destroy",
+        "ca_util_table_update", "ca_util_table_set_added",
+        "ca_mirror_utilization", "ca_scale_down_candidates_create", "ca_scale_down_candidates_info",
+        "ca_scale_down_candidates_fetch", "ca_scale_down_candidates_timings", "ca_scale_down_candidates_destroy",
+        "ca_removal_plan_create_candidates", "ca_multi_create", "ca_multi_destroy",
         "ca_multi_estimate_plan_create", "ca_multi_estimate_plan_run",
         "ca_multi_estimate_plan_stats", "ca_multi_estimate_plan_rerun_units", "ca_multi_estimate_plan_destroy", "ca_multi_estimate_batch",
         "ca_multi_estimate_plan_option_sums", "ca_multi_estimate_plan_option_price_sums",
@@ -536,6 +546,32 @@ class Mirror:
             _check(st, "ca_mirror_node_pods")
             return out[: n.value].tolist()
 
+    # -- scale-down eligibility from the mirror's own state -----------------------
+    def utilization(self, skip_ds: bool, skip_mirror: bool, now_ns: int, node_over=None, pod_over=None,
+                    out: np.ndarray = None, want_drain: bool = False):
+        """utilization.Calculate of every node from the mirror's pods (ca_mirror_utilization):
+        UTIL_INFO rows in position order, and with want_drain also each node's drain bits.
+        node_over = (positions, UTIL_NODE rows), pod_over = (mirror pod ids, UTIL_POD rows):
+        rows that replace the defaults, ids strictly ascending.  out: a caller's (page-locked)
+        result array, else a new one."""
+        n = self.node_count()
+        args, keep = abi.mirror_util_args(skip_ds, skip_mirror, now_ns, node_over, pod_over)
+        if out is None:
+            out = np.zeros(n, abi.UTIL_INFO_DTYPE)
+        drain = np.zeros(n, np.int32) if want_drain else None
+        ms = C.c_float(0)
+        _check(self.lib.ca_mirror_utilization(self.h, C.byref(args), ptr(out), ptr(drain), C.byref(ms)),
+               "ca_mirror_utilization")
+        del keep
+        self.util_kernel_ms = ms.value
+        return (out, drain) if want_drain else out
+
+    def scale_down_candidates(self, skip_ds: bool, skip_mirror: bool, now_ns: int, threshold: float,
+                              gpu_threshold: float, eligible=None, node_over=None,
+                              pod_over=None) -> "ScaleDownCandidates":
+        return ScaleDownCandidates(self, skip_ds, skip_mirror, now_ns, threshold, gpu_threshold, eligible,
+                                   node_over, pod_over)
+
     # -- predicate checker ----------------------------------------------------
     def fits_any_node(self, table: abi.PodTable, pod: int, match=None, last_index: int = 0):
         ms, mask = abi.match_spec(*(match or ()))
@@ -783,9 +819,24 @@ class RemovalPlan:
         p = C.c_void_p()
         _check(self.lib.ca_removal_plan_create(mirror.h, ptr(self.cand), len(self.cand), ptr(mask), ptr(status),
                                                ptr(off), ptr(self.moves), C.byref(p)), "ca_removal_plan_create")
-        self.h = p
+        self._adopt(p)
+
+    def _adopt(self, handle) -> None:
+        self.h = handle
         self.results = np.zeros(len(self.cand), abi.REMOVAL_RESULT_DTYPE)
         self._dest = PinnedArray(self.lib, max(len(self.moves), 1), np.int32)
+
+    @classmethod
+    def from_handle(cls, mirror: Mirror, handle, candidates, move_pods) -> "RemovalPlan":
+        """Wrap a ca_removal_plan the library built itself (ScaleDownCandidates.removal_plan);
+        `candidates` and `move_pods` are its lists, for the result and destination arrays."""
+        self = cls.__new__(cls)
+        self.m = mirror
+        self.lib = mirror.lib
+        self.cand = np.ascontiguousarray(candidates, dtype=np.int32)
+        self.moves = np.ascontiguousarray(move_pods, dtype=np.int32)
+        self._adopt(handle)
+        return self
 
     def run(self, last_index: int = 0, hints=None, want_dest: bool = False) -> RemovalOutput:
         """One sweep.  hints=None: the mirror's resident hints are used and updated
@@ -1373,6 +1424,105 @@ class UtilTable:
         if self.h:
             self.lib.ca_util_table_destroy(self.h)
             self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+@dataclass
+class ScaleDownLists:
+    """ScaleDownCandidates.fetch(): the handle's host lists."""
+    info: np.ndarray            # UTIL_INFO rows per node position
+    node_class: np.ndarray      # abi.CA_SD_* per node position
+    empty: np.ndarray           # class-1 positions, ascending
+    cand: np.ndarray            # class-2 positions, ascending
+    cand_status: np.ndarray     # CA_UNREMOVABLE_BLOCKED_BY_POD or 0 per candidate
+    move_off: np.ndarray        # [n_cand + 1]
+    move_pods: np.ndarray       # mirror pod ids, NodeInfo.Pods order within a candidate
+
+
+class ScaleDownCandidates:
+    """``ca_scale_down_candidates``: utilization from the mirror's own state, the nodes classified
+    against the thresholds and the removal sweep's inputs, built inside the library."""
+
+    def __init__(self, mirror: Mirror, skip_ds: bool, skip_mirror: bool, now_ns: int, threshold: float,
+                 gpu_threshold: float, eligible=None, node_over=None, pod_over=None):
+        self.m = mirror
+        self.lib = mirror.lib
+        self.h = None
+        args, keep = abi.mirror_util_args(skip_ds, skip_mirror, now_ns, node_over, pod_over)
+        el = None if eligible is None else np.ascontiguousarray(eligible, dtype=np.uint8)
+        if el is not None and len(el) != mirror.node_count():
+            raise ValueError("eligible needs one byte per node")
+        h = C.c_void_p()
+        _check(self.lib.ca_scale_down_candidates_create(mirror.h, C.byref(args), float(threshold), float(gpu_threshold),
+                                                        ptr(el), C.byref(h)), "ca_scale_down_candidates_create")
+        del keep
+        self.h = h
+        self._lists = None
+
+    @property
+    def info(self) -> dict:
+        v = [C.c_int32(0) for _ in range(4)]
+        _check(self.lib.ca_scale_down_candidates_info(self.h, *[C.byref(x) for x in v]), "ca_scale_down_candidates_info")
+        return dict(zip(("n_nodes", "n_empty", "n_cand", "n_moves"), (x.value for x in v)))
+
+    def fetch(self) -> ScaleDownLists:
+        if self._lists is None:
+            s = self.info
+            n, nc = s["n_nodes"], s["n_cand"]
+            out = ScaleDownLists(np.zeros(n, abi.UTIL_INFO_DTYPE), np.zeros(n, np.uint8), np.zeros(s["n_empty"], np.int32),
+                                 np.zeros(nc, np.int32), np.zeros(nc, np.int32), np.zeros(nc + 1, np.int32),
+                                 np.zeros(s["n_moves"], np.int32))
+            _check(self.lib.ca_scale_down_candidates_fetch(self.h, ptr(out.info), ptr(out.node_class), ptr(out.empty),
+                                                           ptr(out.cand), ptr(out.cand_status), ptr(out.move_off),
+                                                           ptr(out.move_pods)), "ca_scale_down_candidates_fetch")
+            self._lists = out
+        return self._lists
+
+    def timings(self) -> dict:
+        t = (C.c_float * 7)()
+        self.lib.ca_scale_down_candidates_timings(self.h, t, 7)
+        return {"util_kernel_ms": float(t[0]), "classify_kernel_ms": float(t[1]), "stage_ms": float(t[2]),
+                "move_lists_ms": float(t[3]), "create_ms": float(t[4]), "h2d_bytes": int(t[5]), "d2h_bytes": int(t[6])}
+
+    def removal_plan(self, nodes=None, dest_mask=None) -> "RemovalPlan":
+        """The sweep over every candidate (nodes=None) or over the given class-2 positions in
+        the given order; `dest_mask`: one byte per node (None: every node is a destination)."""
+        n_nodes = self.info["n_nodes"]
+        mask = np.ascontiguousarray(dest_mask if dest_mask is not None else np.ones(n_nodes, np.uint8), dtype=np.uint8)
+        if len(mask) != n_nodes:
+            raise ValueError("dest_mask needs one byte per node")
+        sel = None if nodes is None else np.ascontiguousarray(nodes, dtype=np.int32)
+        if sel is not None and sel.size == 0:
+            sel = np.zeros(1, np.int32)[:0]
+        p = C.c_void_p()
+        st = self.lib.ca_removal_plan_create_candidates(self.h, sel.ctypes.data if sel is not None else None,
+                                                        0 if sel is None else len(sel), ptr(mask), C.byref(p))
+        _check(st, "ca_removal_plan_create_candidates")
+        ls = self.fetch()
+        if sel is None:
+            cand, moves = ls.cand, ls.move_pods
+        else:
+            at = np.searchsorted(ls.cand, sel)
+            cand = sel
+            moves = (np.concatenate([ls.move_pods[ls.move_off[c]:ls.move_off[c + 1]] for c in at])
+                     if len(at) else np.zeros(0, np.int32))
+        return RemovalPlan.from_handle(self.m, p, cand, moves)
+
+    def close(self) -> None:
+        if self.h:
+            self.lib.ca_scale_down_candidates_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
 
     def __del__(self):
         try:

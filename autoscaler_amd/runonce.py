@@ -267,7 +267,7 @@ class UtilInput:
 
 
 def run(backend, util_fn, w: RunOnceWorkload, timers=None, row_zeros=_zeros, expand_fn=None,
-        option_lists: str = "device", pod_groups: str = "host") -> RunOnceResult:
+        option_lists: str = "device", pod_groups: str = "host", scale_down: str = "host") -> RunOnceResult:
     """One loop on `backend` (native.Mirror or pyoracle.OracleState, freshly loaded with
     W.load_filter) with `util_fn(UtilInput, now_ns) -> UTIL_INFO rows` (its attribute `want`,
     default "full", picks the input form); `row_zeros` allocates full utilization rows;
@@ -280,9 +280,17 @@ def run(backend, util_fn, w: RunOnceWorkload, timers=None, row_zeros=_zeros, exp
     them there (`expand_fn` is then called with samples None and `groups=` the handle); "host"
     groups the unschedulable pods in the Python loop.  The device form puts a
     DaemonSet pod in a group of its own (groups.go:68-72), which _equivalence_groups does not: the
-    two agree on a workload whose unschedulable pods carry no CA_POD_DAEMONSET."""
+    two agree on a workload whose unschedulable pods carry no CA_POD_DAEMONSET.
+    `scale_down="device"` (the device mirror only): steps 4 and 5 take utilization, the empty
+    nodes, the candidates and the sweep's plan from one native.ScaleDownCandidates on the
+    mirror's own state: no UtilInput, no `util_fn` call (it may be None) and no host pass over
+    the pods; "host" builds the utilization rows and the move lists in numpy."""
     if pod_groups not in ("host", "device"):
         raise ValueError('pod_groups: "host" or "device"')
+    if scale_down not in ("host", "device"):
+        raise ValueError('scale_down: "host" or "device"')
+    if scale_down == "device" and not callable(getattr(type(backend), "scale_down_candidates", None)):
+        raise TypeError('scale_down="device" needs the device mirror as backend')
     f = w.filt
     r = RunOnceResult()
     clock = time.perf_counter
@@ -358,6 +366,10 @@ def run(backend, util_fn, w: RunOnceWorkload, timers=None, row_zeros=_zeros, exp
     if ps is not None:
         ps.close()
 
+    if scale_down == "device":
+        _scale_down_on_device(backend, w, fo, r, unsched, n_eg, group_off)
+        return r
+
     # 4. scale-down eligibility on the snapshot after step 1
     ui = UtilInput(w, fo.node, getattr(util_fn, "want", "full"), getattr(util_fn, "zeros", row_zeros))
     t = clock()
@@ -399,6 +411,58 @@ def run(backend, util_fn, w: RunOnceWorkload, timers=None, row_zeros=_zeros, exp
                "empty": int(len(r.empty)), "sweep_candidates": int(len(cand)), "pods_to_move": int(len(move_pods)),
                "removable": int(r.sweep_results["removable"].sum())}
     return r
+
+
+def scale_down_overrides(w: RunOnceWorkload, fo):
+    """What the mirror cannot know of the loop's pods: the host's drain verdict.  Every synthetic
+    pod is movable, also the few that carry CA_POD_DAEMONSET (whose default row is not): their
+    override rows, by mirror pod id (running pods 0..P-1, then the filter's placements)."""
+    f = w.filt
+    placed = np.nonzero(fo.node >= 0)[0]
+    run_ds = np.nonzero(f.table.pods["flags"] & abi.CA_POD_DAEMONSET)[0]           # running pod id == record index
+    pend_rec = f.order[placed]
+    new_ds = np.nonzero(f.pending.pods["flags"][pend_rec] & abi.CA_POD_DAEMONSET)[0]
+    if not run_ds.size and not new_ds.size:
+        return None
+    ids = np.concatenate([run_ds, fo.pod_id[placed[new_ds]]]).astype(np.int32)
+    rows = np.zeros(len(ids), abi.UTIL_POD_DTYPE)
+    for col, field in enumerate(("score_milli_cpu", "score_memory")):
+        rows["req_milli"][:, col] = np.concatenate([f.table.pods[field][run_ds], f.pending.pods[field][pend_rec[new_ds]]])
+    rows["req_milli"][:, 1] *= 1000
+    rows["flags"] = abi.CA_UPOD_MOVABLE
+    k = np.argsort(ids, kind="stable")
+    return ids[k], rows[k]
+
+
+def _scale_down_on_device(backend, w: RunOnceWorkload, fo, r: RunOnceResult, unsched, n_eg: int, group_off) -> None:
+    """Steps 4 and 5 of run() from one ScaleDownCandidates handle and its plan."""
+    f = w.filt
+    clock = time.perf_counter
+    over = scale_down_overrides(w, fo)
+    # 4. utilization, classes and lists from the mirror's state after step 1
+    t = clock()
+    sd = backend.scale_down_candidates(False, False, w.now_ns, UTIL_THRESHOLD, UTIL_THRESHOLD, pod_over=over)
+    ls = sd.fetch()
+    r.ms["utilization"] = (clock() - t) * 1e3
+    r.util, r.empty, r.candidates = ls.info, ls.empty, ls.cand
+    # 5. FindNodesToRemove over the handle's candidates, every node a destination, fresh hints
+    placed = np.nonzero(fo.node >= 0)[0]
+    n_ids = max(len(f.table), int(fo.pod_id[placed].max()) + 1 if placed.size else 0)
+    hints = np.full(n_ids, -1, np.int32)
+    t = clock()
+    with sd.removal_plan() as plan:
+        sw = plan.run(r.last_index, hints=hints, want_dest=True)
+    r.ms["sweep"] = (clock() - t) * 1e3
+    sd.close()
+    r.sweep_results, r.sweep_dest = sw.results.copy(), sw.dest.copy()
+    r.sweep_hints = np.asarray(sw.hints)[ls.move_pods].copy()
+    r.last_index = int(sw.last_index)
+    r.ms["total"] = sum(r.ms.values())
+    r.sizes = {"pending": int(len(f.order)), "placed_by_filter": int(placed.size), "unschedulable": int(len(unsched)),
+               "equivalence_groups": n_eg, "options_pairs": int(r.options.size),
+               "estimate_items": int(group_off[-1]), "scale_down_candidates": int(len(ls.empty) + len(ls.cand)),
+               "empty": int(len(ls.empty)), "sweep_candidates": int(len(ls.cand)), "pods_to_move": int(len(ls.move_pods)),
+               "removable": int(r.sweep_results["removable"].sum())}
 
 
 def compare(a: RunOnceResult, b: RunOnceResult) -> dict:

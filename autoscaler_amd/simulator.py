@@ -262,7 +262,18 @@ class RemovalSimulator:
                 ids = {id(p): pid for p, pid in snap.pod_ids(name)}
                 move_ids.extend(ids[id(p)] for p in pods_to_move)
             move_off.append(len(move_ids))
-        # Hints.Get per mirror pod id
+        hints, id_to_pod = self._sweep_hints()
+        before = hints.copy()
+        with unsupported("FindNodesToRemove: the snapshot holds a pod with required anti-affinity"):
+            out = snap.backend.find_nodes_to_remove(np.array(cand_pos, np.int32), mask, np.array(status, np.int32),
+                                                    np.array(move_off, np.int32), np.array(move_ids, np.int32), hints,
+                                                    self.predicate_checker.last_index)
+        return self._finish_sweep(out, candidates, moved_pods, ds_pods, blocking, move_ids, before, id_to_pod)
+
+    def _sweep_hints(self):
+        """Hints.Get per mirror pod id (node positions, -1 none), and the pods by id."""
+        snap = self.cluster_snapshot
+        names = snap.node_names()
         n_ids = max([pid for n in names for _, pid in snap.pod_ids(n)] + [-1]) + 1
         hints = np.full(max(n_ids, 1), -1, np.int32)
         id_to_pod = {pid: p for n in names for p, pid in snap.pod_ids(n)}
@@ -270,11 +281,14 @@ class RemovalSimulator:
             node, ok = self.hints.Get(Hints.key(p))
             if ok and node in snap._state.pos:
                 hints[pid] = snap.position(node)
-        before = hints.copy()
-        with unsupported("FindNodesToRemove: the snapshot holds a pod with required anti-affinity"):
-            out = snap.backend.find_nodes_to_remove(np.array(cand_pos, np.int32), mask, np.array(status, np.int32),
-                                                    np.array(move_off, np.int32), np.array(move_ids, np.int32), hints,
-                                                    self.predicate_checker.last_index)
+        return hints, id_to_pod
+
+    def _finish_sweep(self, out, candidates: list, moved_pods: list, ds_pods: list, blocking: list, move_ids: list,
+                      before, id_to_pod: dict):
+        """A sweep's RemovalOutput back into the reference's terms: lastIndex, Hints.Set, and the
+        (to_remove, unremovable) lists in candidate order."""
+        snap = self.cluster_snapshot
+        names = snap.node_names()
         cut = next((c for c in range(len(candidates))
                     if int(out.results[c]["reason"]) == abi.CA_UNREMOVABLE_OUT_OF_SCOPE), None)
         if cut is not None:
@@ -299,6 +313,30 @@ class RemovalSimulator:
                 unremovable.append(UnremovableNode(node, reason, blocking[c] if reason == BlockedByPod else None))
         self.last_stats = out
         return to_remove, unremovable
+
+    def FindNodesToRemovePlanned(self, plan, candidates: list, verdicts: dict):  # noqa: N802
+        """FindNodesToRemove over `candidates` (node names) with the sweep's inputs already in a
+        native.RemovalPlan the library built from its own lists (ScaleDownCandidates.removal_plan
+        over the candidates' positions, in this order).  verdicts[name] is the node's
+        GetPodsToMove result (pods_to_move, daemonset pods, blocking pod, error), which the
+        handle's pod overrides were made from.  Every candidate must be a destination."""
+        snap = self.cluster_snapshot
+        moved_pods, ds_pods, blocking, move_ids = [], [], [], []
+        for name in candidates:
+            pods_to_move, ds, block, err = verdicts[name]
+            moved_pods.append(pods_to_move if err is None else [])
+            ds_pods.append(ds)
+            blocking.append(block)
+            if err is None:
+                ids = {id(p): pid for p, pid in snap.pod_ids(name)}
+                move_ids.extend(ids[id(p)] for p in pods_to_move)
+        if not np.array_equal(plan.moves, np.array(move_ids, np.int32)):
+            raise RuntimeError("FindNodesToRemovePlanned: the plan's pods to move differ from the host verdicts")
+        hints, id_to_pod = self._sweep_hints()
+        before = hints.copy()
+        with unsupported("FindNodesToRemove: the snapshot holds a pod with required anti-affinity"):
+            out = plan.run(self.predicate_checker.last_index, hints=hints, want_dest=True)
+        return self._finish_sweep(out, candidates, moved_pods, ds_pods, blocking, move_ids, before, id_to_pod)
 
     def SimulateNodeRemovals(self, candidates: list, destinations, timestamp: float = 0.0,  # noqa: N802
                              pdb_tracker=None, limit: int = 0):

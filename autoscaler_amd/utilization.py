@@ -153,6 +153,59 @@ def CalculateAll(node_infos: list, skip_daemonset_pods: bool, skip_mirror_pods: 
     return [info_from_row(out[i], ni.node.name, gc) for i, (ni, gc) in enumerate(zip(node_infos, gpu_configs))]
 
 
+def snapshot_overrides(snapshot, names: list, gpu_configs: dict, pod_flags=None):
+    """The rows ca_mirror_utilization cannot derive from the mirror, for the nodes `names` of
+    `snapshot`: (node_over, pod_over) as native.Mirror.utilization takes them, or None where
+    there are none.  A node gets a row when it has a GpuConfig or lacks cpu / memory; a pod when
+    it is a mirror pod, deleted, or requests its node's GPU resource.  `pod_flags(pod) -> int`
+    (CA_UPOD_MOVABLE / _BLOCKING, or None to keep the default) adds the host's drain verdict: a
+    pod whose verdict differs from the default row's gets a row too."""
+    npos, nrows, pids, prows = [], [], [], []
+    for name in names:
+        node = snapshot.Get(name).node
+        gc = gpu_configs.get(name)
+        if gc is not None or ResourceCPU not in node.allocatable or ResourceMemory not in node.allocatable:
+            npos.append(snapshot.position(name))
+            nrows.append(node_row(node, gc))
+        res = gc.resource_name if gc else None
+        for p, pid in snapshot.pod_ids(name):
+            ds = is_daemonset_pod(p)
+            default = abi.CA_UPOD_DAEMONSET if ds else abi.CA_UPOD_MOVABLE
+            drain = pod_flags(p) if pod_flags is not None else None
+            special = (is_mirror_pod(p) or p.deletion_timestamp is not None or
+                       (res is not None and any(res in c.requests for c in p.containers)))
+            if not special and (drain is None or drain == (default & abi.CA_UPOD_MOVABLE)):
+                continue
+            r = pod_row(p, res)
+            r["flags"] |= (default & abi.CA_UPOD_MOVABLE) if drain is None else drain
+            pids.append(pid)
+            prows.append(r)
+    node_over = pod_over = None
+    if npos:
+        k = np.argsort(npos)
+        node_over = (np.array(npos, np.int32)[k], np.array(nrows, abi.UTIL_NODE_DTYPE)[k])
+    if pids:
+        k = np.argsort(pids)
+        pod_over = (np.array(pids, np.int32)[k], np.array(prows, abi.UTIL_POD_DTYPE)[k])
+    return node_over, pod_over
+
+
+def CalculateAllOnSnapshot(snapshot, node_infos: list, skip_daemonset_pods: bool,  # noqa: N802
+                           skip_mirror_pods: bool, gpu_configs: Optional[list], current_time: float):
+    """CalculateAll for NodeInfos of `snapshot`, from the mirror's own state
+    (ca_mirror_utilization): no table is built; only override rows for what the mirror cannot
+    know cross to the device.  Same return as CalculateAll."""
+    from .native import Mirror
+    if not isinstance(snapshot.backend, Mirror):
+        raise TypeError("CalculateAllOnSnapshot needs the device mirror as the snapshot's backend")
+    gpu_configs = gpu_configs if gpu_configs is not None else [None] * len(node_infos)
+    names = [ni.node.name for ni in node_infos]
+    node_over, pod_over = snapshot_overrides(snapshot, names, dict(zip(names, gpu_configs)))
+    out = snapshot.backend.utilization(skip_daemonset_pods, skip_mirror_pods, round(current_time * 1e9),
+                                       node_over, pod_over)
+    return [info_from_row(out[snapshot.position(n)], n, gc) for n, gc in zip(names, gpu_configs)]
+
+
 def Calculate(node_info, skip_daemonset_pods: bool, skip_mirror_pods: bool,  # noqa: N802
               gpu_config: Optional[GpuConfig], current_time: float):
     """utilization.Calculate (info.go:48-81) for one node: returns (Info, error)."""

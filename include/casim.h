@@ -691,7 +691,10 @@ int ca_mirror_sync_stats(const ca_mirror* m, int64_t* out, int32_t cap);
  *     records, template rows and group lists only, nothing by node position: they stay valid
  *     and give exactly the results of objects created after the reorder.
  *   ca_util_table is the caller's own table by node index, not the mirror's: out of scope,
- *     the caller rebuilds or re-indexes it. */
+ *     the caller rebuilds or re-indexes it.  ca_mirror_utilization reads the mirror itself and
+ *     stores nothing between calls: it follows the new order with no hook.
+ *   ca_scale_down_candidates holds positions in the old order: ca_removal_plan_create_candidates
+ *     returns CA_ESTATE; create a new handle. */
 int ca_mirror_reorder_nodes(ca_mirror* m, const int32_t* order, int32_t n);
 /* out[0] reorders since create/Clear, [1] of them permuted on the device (rows were
  * resident), [2] device time of the last one in microseconds; returns 3. */
@@ -843,6 +846,70 @@ int ca_util_table_set_added(ca_util_table* t, const int32_t* node, const ca_util
 int ca_util_calculate(ca_util_table* t, int32_t skip_daemonset_pods, int32_t skip_mirror_pods,
                       int64_t now_ns, ca_util_info* out, float* kernel_ms);
 int ca_util_device_results(const ca_util_table* t, const ca_util_info** out);
+
+/* ---- scale-down eligibility from the mirror -----------------------------------
+ * The same rows as ca_util_calculate, byte for byte, computed from the mirror's own state
+ * instead of a table the caller builds: node position i's pods are the mirror pods now on it
+ * (inside forks, after reverts, removals and reorders), so a loop needs no ca_util_table and
+ * no second copy of FilterOutSchedulable's placements.
+ *  default rows  a node is alloc_milli = {alloc_milli_cpu, alloc_memory * 1000, 0} with
+ *                CA_UNODE_HAS_CPU | CA_UNODE_HAS_MEM; a pod is req_milli = {score_milli_cpu,
+ *                score_memory * 1000, 0} (the containers-only sums utilization.Calculate adds
+ *                up, info.go:100-124) with flags CA_UPOD_DAEMONSET alone when its record has
+ *                CA_POD_DAEMONSET, else CA_UPOD_MOVABLE alone.  A default node whose
+ *                alloc_memory * 1000 does not fit int64: CA_EUNSUPPORTED.
+ *  overrides     node_rows[k] replaces the whole row of node position node_pos[k], pod_rows[k]
+ *                that of mirror pod pod_ids[k]: what the mirror cannot know (mirror-pod flag,
+ *                deletion time and grace, the host's drain verdict, GPU config and requests,
+ *                absent allocatable).  node_pos and pod_ids are strictly ascending and in range,
+ *                else CA_EINVAL with out and out_drain untouched; an override for a pod that is
+ *                on no node is accepted and ignored.  Overrides last for this call only.
+ *  out           [n_nodes] rows, written by the kernel itself when page-locked (ca_host_alloc),
+ *                else by a copy; NULL keeps them in HBM.  out_drain[n_nodes] (may be NULL): the
+ *                OR of CA_UPOD_MOVABLE | CA_UPOD_BLOCKING over the node's pods.
+ *  *kernel_ms    (may be NULL) device time of the two kernels. */
+typedef struct ca_mirror_util_args {
+    int32_t skip_daemonset_pods, skip_mirror_pods;
+    int64_t now_ns;
+    const int32_t* node_pos;  const ca_util_node* node_rows; int32_t n_node_rows;  /* overrides */
+    const int32_t* pod_ids;   const ca_util_pod*  pod_rows;  int32_t n_pod_rows;   /* overrides */
+} ca_mirror_util_args;
+int ca_mirror_utilization(ca_mirror* m, const ca_mirror_util_args* a, ca_util_info* out, int32_t* out_drain,
+                          float* kernel_ms);
+
+/* The nodes classified for scale-down: ca_mirror_utilization with `a`, then per node, first
+ * match wins: */
+#define CA_SD_INELIGIBLE  4   /* eligible[i] == 0 (eligible NULL: every node is eligible)       */
+#define CA_SD_UTIL_ERROR  3   /* status != CA_UTIL_OK                                            */
+#define CA_SD_NOT_BELOW   0   /* utilization >= t: t = gpu_threshold when resource == CA_UTIL_GPU,
+                                 else threshold (eligibility.go:158-178; NaN counts as below)    */
+#define CA_SD_EMPTY       1   /* below, drain bits 0: FindEmptyNodesToRemove lists it            */
+#define CA_SD_CANDIDATE   2   /* below, not empty                                                */
+/* empty[n_empty] and cand[n_cand] hold the class-1 and class-2 positions in ascending order;
+ * cand_status[c] is CA_UNREMOVABLE_BLOCKED_BY_POD when candidate c's drain bits hold
+ * CA_UPOD_BLOCKING, else 0; move_pods[move_off[c] .. move_off[c+1]) are its pods whose row
+ * (default or override) has CA_UPOD_MOVABLE, in NodeInfo.Pods order: ca_removal_plan_create's
+ * inputs.  The handle is a snapshot of the moment of create; fetch arrays may each be NULL.
+ * Every CA_EINVAL leaves *out untouched.
+ * timings: [0] device time of the utilization kernels, [1] of the classification and
+ * compaction (ms), [2] host time of the pod -> node staging fill, [3] of the move lists, [4] of
+ * the whole create (ms), [5] bytes copied to the device, [6] bytes copied back; returns 7. */
+typedef struct ca_scale_down_candidates ca_scale_down_candidates;
+int ca_scale_down_candidates_create(ca_mirror* m, const ca_mirror_util_args* a,
+        double threshold, double gpu_threshold, const uint8_t* eligible /* [n_nodes] or NULL = all */,
+        ca_scale_down_candidates** out);
+int ca_scale_down_candidates_info(const ca_scale_down_candidates* h, int32_t* n_nodes, int32_t* n_empty,
+                                  int32_t* n_cand, int32_t* n_moves);
+int ca_scale_down_candidates_fetch(const ca_scale_down_candidates* h, ca_util_info* info, uint8_t* node_class,
+        int32_t* empty, int32_t* cand, int32_t* cand_status, int32_t* move_off, int32_t* move_pods);
+int ca_scale_down_candidates_timings(const ca_scale_down_candidates* h, float* out, int32_t cap);
+int ca_scale_down_candidates_destroy(ca_scale_down_candidates* h);
+/* ca_removal_plan_create on the handle's lists, which never leave the library.  nodes NULL:
+ * every class-2 node in position order.  Otherwise the n given positions in the given order
+ * (legacy's two sweeps over a subset): each must be class 2 and unique, else CA_EINVAL and no
+ * plan.  CA_ESTATE for a handle created before a ca_mirror_reorder_nodes. */
+int ca_removal_plan_create_candidates(const ca_scale_down_candidates* h, const int32_t* nodes, int32_t n,
+        const uint8_t* dest_mask, ca_removal_plan** out);
 
 /* ---- multi-GPU ---------------------------------------------
  * One mirror per device (ca_mirror_create(device)), kept identical by the caller: every
