@@ -300,15 +300,8 @@ int plan_removals(ca_mirror* m, const int32_t* candidates, int32_t C, const uint
         for (int32_t i = 0; i < M; i++) bad |= (uint32_t)((uint32_t)move_pods[i] >= (uint32_t)n_pods);
         if (bad) return CA_EINVAL;
     }
-    {   // the planner walks unique node names (planner.go:261)
-        std::vector<uint8_t> seen((size_t)std::max(N, 1), 0);
-        for (int32_t c = 0; c < C; c++) {
-            const int32_t nd = candidates[c];
-            if (nd < 0 || nd >= N) continue;
-            if (seen[nd]) return CA_EINVAL;
-            seen[nd] = 1;
-        }
-    }
+    // A node may be listed more than once: each listing is simulated on the snapshot as it then
+    // is (UNEXPECTED_ERROR once an earlier listing removed it: outside podDestinations).
     if (C == 0) {
         if (n_moves) *n_moves = 0;
         ps.total_ms = 0;
@@ -428,6 +421,7 @@ int plan_removals(ca_mirror* m, const int32_t* candidates, int32_t C, const uint
             const int32_t* list = w_pods.data() + mo;
             const int64_t lout = k + 1 < j ? (int64_t)w_res[k + 1 - i].last_index_in : (int64_t)Ls;
             if (node >= 0 && node < N && gained[node]) { conflict = true; why = "grown"; break; }   // its pods to move grew
+            if (node >= 0 && node < N && gone[node]) { conflict = true; why = "removed"; break; }   // listed again: no candidate now
             ca_plan_result& r = results[k];
             std::memset(&r, 0, sizeof r);
             r.last_index_in = (int32_t)L;

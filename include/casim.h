@@ -1211,7 +1211,10 @@ int ca_intern_compile_term(ca_interner* it, const ca_requirement_str* reqs, int3
  * caller-given pods followed by the copies committed onto it, in commit order (NodeInfo.Pods
  * appends).  The loop stops before the next candidate once max_removable candidates are
  * removable (planner.go:268-271, unneededNodesLimit; <= 0: no limit); the rest are
- * CA_UNREMOVABLE_NOT_RUN.  Prefix protocol and kernel scope as ca_find_nodes_to_remove. */
+ * CA_UNREMOVABLE_NOT_RUN.  Prefix protocol and kernel scope as ca_find_nodes_to_remove.
+ * A node may be listed more than once (the reference walks unique names, planner.go:261):
+ * every listing is simulated on the snapshot as it then is, so a node that an earlier listing
+ * removed is CA_UNREMOVABLE_UNEXPECTED_ERROR (outside the destination set, cluster.go:157-160). */
 typedef struct ca_plan_result {
     int32_t  removable;                       /* NodeToBeRemoved, committed              */
     int32_t  reason;                          /* CA_UNREMOVABLE_*                        */

@@ -149,6 +149,10 @@ def plan_by_steps(o, case: PlanCase) -> dict:
         one = o.find_nodes_to_remove(np.array([node], np.int32), mask, np.zeros(1, np.int32),
                                      np.array([0, len(lst)], np.int32), np.array(lst, np.int32), H, L)
         sr = one.results[0]
+        if sr["reason"] == abi.CA_UNREMOVABLE_OUT_OF_SCOPE:                     # casim.h scope: the prefix cut
+            r["reason"] = abi.CA_UNREMOVABLE_OUT_OF_SCOPE
+            cut = True
+            continue
         H, L = one.hints.copy(), one.last_index
         r["n_placed"] = sr["n_placed"]
         r["evals"] = sr["evals"]
