@@ -95,6 +95,8 @@ class ClusterSnapshot:
         self._token = object()            # this snapshot, in the replicas' stamps
         self._version = 0                 # bumped by everything that changes the log or its encoding
         self.replica_loads = 0            # sync_replica calls that reloaded their mirror
+        self.backend_clears = 0           # backend.clear() calls (replays, Clear): what lives on the mirror
+                                          # beside the log (its resident pod util rows) is gone after each
 
     # -- encoding / replay ------------------------------------------------------
     def _sizes(self):
@@ -116,6 +118,7 @@ class ClusterSnapshot:
         self._stack = []
         self._version += 1
         self.backend.clear()
+        self.backend_clears += 1
         for op in log:
             self._apply(op)
 
@@ -253,6 +256,7 @@ class ClusterSnapshot:
 
     def Clear(self) -> None:  # noqa: N802
         self.backend.clear()
+        self.backend_clears += 1
         self._log = []
         self._state = _State()
         self._stack = []

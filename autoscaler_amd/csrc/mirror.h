@@ -5,7 +5,9 @@
 // device rows are re-synchronised lazily (dirty rows only) before a kernel reads them.
 #pragma once
 #include "casim_internal.h"
+#include "podcols_host.h"
 #include <array>
+#include <memory>
 #include <deque>
 #include <cstdlib>
 #include <new>
@@ -123,8 +125,31 @@ struct UtilScratch {
     DevBuf cls;                    // ca_scale_down_candidates_create: [counts | empty | cand | status | class]
     HostBuf h_cls;
     int32_t n_nodes = 0;           // rows valid in info / drain
-    float stage_ms = 0;            // host time of the last call's pod -> node staging fill
+    float stage_ms = 0;            // host time of the last call's pod -> node staging fill (resident: the column sync)
+    size_t table_pods = 0;         // resident calls: pods on nodes (the slot table's upper bound)
     int64_t h2d_bytes = 0, d2h_bytes = 0;   // bytes the last call moved across PCIe
+};
+
+// The resident per-pod columns (podcols.hip): each mirror pod's node, its slot in the node's
+// NodeInfo.Pods list and the util row its caller set.  They exist from the first call of a
+// resident entry point until ca_mirror_clear; the host rows stay authoritative and
+// ca_mirror::sync_pod_cols brings the device copy up to date before a kernel reads it.
+struct PodCols {
+    PodColDirty dirty;             // node / slot entries
+    PodColDirty rdirty;            // util rows and has-row flags (same `synced`)
+    PodRowTable rows;              // the host copy of the util rows
+    DevBuf d_node, d_slot, d_has, d_row;   // [cap] int32, int32, uint8, ca_util_pod
+    size_t cap = 0;
+    DevBuf d_stage;                // one sync's scatter entries
+    HostBuf h_stage;               // one sync's ranges and entries, page-locked
+    DevBuf d_mv;                   // ca_scale_down_candidates_create_resident: maps, table, lists
+    HostBuf h_mv;
+    hipEvent_t ev = nullptr;       // after the move-list kernels
+    enum { ST_FULL = 0, ST_STAGED, ST_ENTRIES, ST_TAIL, ST_REORDERS, ST_SHIFTS, ST_ROWS, ST_BYTES, ST_N };
+    int64_t stat[ST_N] = {0};      // ca_mirror_pod_column_stats
+    ~PodCols() {
+        if (ev) (void)hipEventDestroy(ev);
+    }
 };
 
 // Dirty-row staging of sync_nodes: one H2D copy + a scatter kernel.
@@ -312,6 +337,15 @@ struct ca_mirror {
     casim::DevBuf d_pod_hints;
     size_t d_hints_n = 0;
     int ensure_pod_hints();                // grow to pods.size(), new entries -1
+    // resident per-pod columns (podcols.hip); null until a resident entry point is called
+    std::unique_ptr<casim::PodCols> pcol;
+    int ensure_pod_cols();                 // bring them into being (all dirty)
+    int sync_pod_cols();                   // push stale entries, the tail and changed util rows
+    int reorder_pod_cols(const int32_t* d_inv, int32_t n);   // node column through the inverse permutation
+    void pcol_mark(int32_t pod) { if (pcol) pcol->dirty.mark(pod); }
+    void pcol_mark_node(int32_t node) {    // every pod now on `node`
+        if (pcol) for (int32_t id : nodes[node].pods) pcol->dirty.mark(id);
+    }
     int64_t n_ext_pods = 0;                // pods stored with host ports / extended requests
     int64_t n_eph_pods = 0;                // pods stored with ephemeral-storage requests
     int64_t n_oos_pods = 0;                // pods stored with CA_POD_OUT_OF_SCOPE (never decremented:

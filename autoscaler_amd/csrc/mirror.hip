@@ -525,6 +525,7 @@ void ca_mirror::add_pod_to_node(int32_t pod, int32_t node) {
     node_apply(node, pods[pod].spec, +1);
     nodes[node].pods.push_back(pod);
     pods[pod].node = node;
+    pcol_mark(pod);                          // (a new id is the columns' tail: not marked)
     journal_push(J_ADD_POD, node, pod, (int32_t)nodes[node].pods.size() - 1, before);
 }
 
@@ -1145,6 +1146,7 @@ int ca_mirror_clear(ca_mirror* m) {
     m->all_dirty = true; m->static_dirty = true; m->d_rows = 0;
     m->d_pods_synced = 0; m->d_terms_synced = 0;
     m->d_hints_n = 0;
+    m->pcol.reset();                         // the per-pod columns and their resident rows go with the pods
     for (int64_t& c : m->sync_stat) c = 0;
     for (int64_t& c : m->reorder_stat) c = 0;
     return CA_OK;
@@ -1222,6 +1224,8 @@ int ca_mirror_remove_pod(ca_mirror* m, int32_t pod_id) {
     nd.pods.pop_back();
     m->node_apply(node, m->pods[pod_id].spec, -1);
     m->pods[pod_id].node = -1;
+    m->pcol_mark(pod_id);
+    if ((size_t)slot < nd.pods.size()) m->pcol_mark(nd.pods[slot]);   // the swapped-in pod changed slot
     m->journal_push(J_REMOVE_POD, node, pod_id, slot, before);
     return CA_OK;
 }
@@ -1237,6 +1241,7 @@ int ca_mirror_remove_node(ca_mirror* m, int32_t node_pos) {
         if (m->pods[id].spec.flags & CA_POD_REQUIRED_ANTI_AFFINITY) m->n_scope_blockers--;
     }
     for (size_t i = 0; i < m->pods.size(); i++) if (m->pods[i].node > node_pos) m->pods[i].node--;
+    if (m->pcol) m->pcol->dirty.mark_full();                   // positions moved: the node column goes up whole
     // positions moved: every row is re-uploaded before the next kernel
     m->dirty_rows.clear();
     m->dirty_flag.assign(m->nodes.size(), 0);
@@ -1276,10 +1281,12 @@ int ca_mirror_reorder_nodes(ca_mirror* m, const int32_t* order, int32_t n) {
     // rows resident and current apart from a few dirty ones: permuted on the device
     const bool resident = N > 0 && m->d_rows == N && !m->all_dirty && !m->static_dirty;
     const bool hints = N > 0 && m->d_hints_n > 0;
+    // the pod -> node column, in sync or with dirty entries pending (they go up later, from the new host state)
+    const bool cols = N > 0 && m->pcol && !m->pcol->dirty.full && m->pcol->dirty.synced > 0;
     const size_t ob = (sizeof(int32_t) * N + 15) & ~(size_t)15;       // order | inverse, 16-byte aligned
     int32_t* inv = nullptr;
     std::vector<int32_t> inv_host;
-    if (resident || hints) {
+    if (resident || hints || cols) {
         // (an earlier reorder's copy out of the staging is done)
         CA_HIP_CHECK(hipStreamSynchronize(m->stream));
         if ((rc = m->h_reorder.reserve(2 * ob)) != CA_OK) return rc;
@@ -1319,7 +1326,7 @@ int ca_mirror_reorder_nodes(ca_mirror* m, const int32_t* order, int32_t n) {
     m->order_epoch++;
     m->reorder_stat[ca_mirror::RS_CALLS]++;
     m->reorder_stat[ca_mirror::RS_LAST_US] = 0;
-    if (!resident && !hints) return CA_OK;
+    if (!resident && !hints && !cols) return CA_OK;
     char* const d = m->d_reorder.as<char>();
     const int32_t* d_order = reinterpret_cast<const int32_t*>(d);
     const int32_t* d_inv = reinterpret_cast<const int32_t*>(d + ob);
@@ -1346,6 +1353,7 @@ int ca_mirror_reorder_nodes(ca_mirror* m, const int32_t* order, int32_t n) {
                            m->d_pod_hints.as<int32_t>(), (int32_t)m->d_hints_n, d_inv, n);
         CA_HIP_CHECK(hipGetLastError());
     }
+    if (cols && (rc = m->reorder_pod_cols(d_inv, n)) != CA_OK) return rc;
     CA_HIP_CHECK(hipEventRecord(m->ev1, m->stream));
     CA_HIP_CHECK(hipStreamSynchronize(m->stream));
     float ms = 0;
@@ -1387,6 +1395,7 @@ int ca_mirror_revert(ca_mirror* m) {
             std::memcpy(m->nodes[e.node].ports, e.ports, sizeof e.ports);
             m->nodes[e.node].pods.pop_back();
             m->pods[e.pod].node = -1;
+            m->pcol_mark(e.pod);
         } else if (e.kind == J_REMOVE_POD) {
             NodeRow& nd = m->nodes[e.node];
             m->node_apply(e.node, m->pods[e.pod].spec, +1);
@@ -1396,8 +1405,10 @@ int ca_mirror_revert(ca_mirror* m) {
             } else {
                 nd.pods.push_back(nd.pods[e.slot]);
                 nd.pods[e.slot] = e.pod;
+                m->pcol_mark(nd.pods.back());                  // the swapped-in pod goes back to the end
             }
             m->pods[e.pod].node = e.node;
+            m->pcol_mark(e.pod);
         } else if (e.kind == J_REMOVE_NODE) {
             const int32_t pos = e.node;
             for (size_t i = 0; i < m->pods.size(); i++) if (m->pods[i].node >= pos) m->pods[i].node++;
@@ -1407,6 +1418,7 @@ int ca_mirror_revert(ca_mirror* m) {
                 m->pods[id].node = pos;
                 if (m->pods[id].spec.flags & CA_POD_REQUIRED_ANTI_AFFINITY) m->n_scope_blockers++;
             }
+            if (m->pcol) m->pcol->dirty.mark_full();
             m->dirty_rows.clear();
             m->dirty_flag.assign(m->nodes.size(), 0);
             m->all_dirty = true;

@@ -95,6 +95,7 @@ int32_t ca_mirror::store_moved_copy(int32_t pod) {
     if (row.spec.req_ephemeral != 0) n_eph_pods++;
     if (row.spec.flags & CA_POD_OUT_OF_SCOPE) n_oos_pods++;
     pods.push_back(row);
+    if (pcol) pcol->rows.inherit((int32_t)pods.size() - 1, pod);   // the same pod object: its util row moves with it
     return (int32_t)pods.size() - 1;
 }
 
@@ -259,6 +260,15 @@ int ca_mirror::replay_moves(const ca_plan_move* mv, int32_t nm) {
         n_scope_blockers += pt.blockers;
         dirty_rows.insert(dirty_rows.end(), pt.dirty.begin(), pt.dirty.end());
         if (journaled) journal.insert(journal.end(), pt.jr.begin(), pt.jr.end());
+    }
+    if (pcol) {
+        // the copies are the columns' tail; the removed pods and whoever is left on their nodes
+        // (a swap-with-last moved some of them) are stale
+        for (int32_t t = 0; t < nm; t++) {
+            pcol->dirty.mark(mv[t].pod);
+            pcol_mark_node(src_node[t]);
+            pcol->rows.inherit(base + t, root[t]);
+        }
     }
     tmark("merged");
     return first_rc;

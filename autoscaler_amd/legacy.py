@@ -121,13 +121,21 @@ class ScaleDown:
 
     def __init__(self, snapshot: ClusterSnapshot, removal_simulator: sim.RemovalSimulator, node_groups: dict,
                  options: ScaleDownOptions, gpu_configs: Optional[dict] = None,
-                 calculate_all: Optional[Callable] = None, device_candidates: bool = False):
+                 calculate_all: Optional[Callable] = None, device_candidates: bool = False,
+                 resident_rows: bool = False):
+        if resident_rows and not device_candidates:
+            raise ValueError("resident_rows=True needs device_candidates=True")
         if device_candidates:
             from .native import Mirror
             if not isinstance(snapshot.backend, Mirror):
                 raise TypeError("device_candidates=True needs the device mirror as the snapshot's backend")
         self.device_candidates = device_candidates
         self.device_updates = 0                        # UpdateUnneededNodes calls served by the candidates handle
+        # resident_rows: the pod rows stay on the mirror (Mirror.set_pod_util_rows); each loop sends
+        # the new and changed ones and clears those that went away
+        self.resident_rows = resident_rows
+        self._row_ids: set = set()                     # mirror pod ids that hold a row of ours ...
+        self._row_clears = None                        # ... on the mirror as of this snapshot.backend_clears
         self.snapshot = snapshot
         self.removal_simulator = removal_simulator
         self.node_groups = node_groups                 # node name -> NodeGroup (NodeGroupForNode)
@@ -236,7 +244,9 @@ class ScaleDown:
         FindNodesToRemove, or None when a host verdict has no form in the handle (a drain error
         without a blocking pod, a utilization error, a candidate that is no destination, an empty
         node beyond its group's limits): the caller then takes the host path.  Changes nothing
-        before it returns."""
+        before it returns, except that with resident_rows the loop's pod rows are on the mirror
+        by then (also when it returns None after the handle was made: the host path reads none
+        of them, and the next loop sends what differs)."""
         import numpy as np
         from . import abi
         from .drain import get_pods_to_move
@@ -262,9 +272,13 @@ class ScaleDown:
                 flag[id(v[2].pod)] = abi.CA_UPOD_BLOCKING
         node_over, pod_over = utilization.snapshot_overrides(snap, list(verdicts), self.gpu_configs,
                                                              pod_flags=lambda p: flag.get(id(p), 0))
+        if self.resident_rows:
+            self._send_changed_rows(pod_over)
+            pod_over = None
         sd = snap.backend.scale_down_candidates(
             opt.ignore_daemonsets_utilization, opt.ignore_mirror_pods_utilization, round(timestamp * 1e9),
-            opt.scale_down_utilization_threshold, opt.scale_down_gpu_utilization_threshold, eligible, node_over, pod_over)
+            opt.scale_down_utilization_threshold, opt.scale_down_gpu_utilization_threshold, eligible, node_over, pod_over,
+            resident=self.resident_rows)
         ls = sd.fetch()
         if (ls.node_class == abi.CA_SD_UTIL_ERROR).any():
             sd.close()
@@ -295,6 +309,34 @@ class ScaleDown:
                 return rs.FindNodesToRemovePlanned(plan, cands, verdicts)
         sweep.close = sd.close
         return unneeded, util_map, ineligible, within, sweep
+
+    def _send_changed_rows(self, pod_over) -> None:
+        """This loop's pod rows as resident rows: only what differs from what the mirror holds.
+        What it holds is read from the mirror's own host copy (Mirror.pod_util_rows), not
+        remembered here: a replay or a Clear of the snapshot clears the backend, the rows go with
+        it, and the same pod ids come back without them.  Only the ids to clear are remembered,
+        and forgotten when snapshot.backend_clears says the mirror started over."""
+        import numpy as np
+        from . import abi
+        snap, m = self.snapshot, self.snapshot.backend
+        if self._row_clears != snap.backend_clears:
+            self._row_ids, self._row_clears = set(), snap.backend_clears
+        if pod_over is None:
+            ids, rows = np.zeros(0, np.int32), np.zeros(0, abi.UTIL_POD_DTYPE)
+        else:
+            ids = np.ascontiguousarray(pod_over[0], dtype=np.int32)
+            rows = np.ascontiguousarray(pod_over[1], dtype=abi.UTIL_POD_DTYPE)
+        held, has = m.pod_util_rows(ids)
+        width = abi.UTIL_POD_DTYPE.itemsize
+        same = (held.view(np.uint8).reshape(-1, width) == rows.view(np.uint8).reshape(-1, width)).all(axis=1)
+        changed = np.nonzero((has == 0) | ~same)[0]
+        now = set(ids.tolist())
+        gone = sorted(self._row_ids - now)
+        if changed.size:
+            m.set_pod_util_rows(ids[changed], rows[changed])
+        if gone:
+            m.set_pod_util_rows(np.array(gone, np.int32), None)
+        self._row_ids = now
 
     def UpdateUnneededNodes(self, destination_nodes: list, scale_down_candidates: list,  # noqa: N802
                             timestamp: float) -> None:

@@ -156,6 +156,13 @@ def load() -> C.CDLL:
         "ca_scale_down_candidates_fetch": ([vp, vp, vp, vp, vp, vp, vp, vp], C.c_int),
         "ca_scale_down_candidates_timings": ([vp, p(C.c_float), i32], C.c_int),
         "ca_scale_down_candidates_destroy": ([vp], C.c_int),
+        "ca_mirror_set_pod_util_rows": ([vp, vp, vp, i32], C.c_int),
+        "ca_mirror_get_pod_util_rows": ([vp, vp, vp, vp, i32], C.c_int),
+        "ca_mirror_utilization_resident": ([vp, vp, vp, vp, p(C.c_float)], C.c_int),
+        "ca_scale_down_candidates_create_resident": ([vp, vp, C.c_double, C.c_double, vp, p(vp)], C.c_int),
+        "ca_mirror_fetch_pod_columns": ([vp, vp, vp, i32], C.c_int),
+        "ca_mirror_pod_column_stats": ([vp, p(C.c_int64), i32], C.c_int),
+        "ca_mirror_pod_count": ([vp, p(i32)], C.c_int),
         "ca_removal_plan_create_candidates": ([vp, vp, i32, vp, p(vp)], C.c_int),
         "ca_multi_create": ([p(vp), i32, p(vp)], C.c_int),
         "ca_multi_destroy": ([vp], C.c_int),
@@ -261,6 +268,9 @@ def exported_symbols() -> list[str]:
         "ca_mirror_utilization", "ca_scale_down_candidates_create", "ca_scale_down_candidates_info",
         "ca_scale_down_candidates_fetch", "ca_scale_down_candidates_timings", "ca_scale_down_candidates_destroy",
         "ca_removal_plan_create_candidates", "ca_multi_create", "ca_multi_destroy",
+        "ca_mirror_set_pod_util_rows", "ca_mirror_get_pod_util_rows", "ca_mirror_utilization_resident",
+        "ca_scale_down_candidates_create_resident", "ca_mirror_fetch_pod_columns", "ca_mirror_pod_column_stats",
+        "ca_mirror_pod_count",
         "ca_multi_estimate_plan_create", "ca_multi_estimate_plan_run",
         "ca_multi_estimate_plan_stats", "ca_multi_estimate_plan_rerun_units", "ca_multi_estimate_plan_destroy", "ca_multi_estimate_batch",
         "ca_multi_estimate_plan_option_sums", "ca_multi_estimate_plan_option_price_sums",
@@ -548,29 +558,75 @@ class Mirror:
 
     # -- scale-down eligibility from the mirror's own state -----------------------
     def utilization(self, skip_ds: bool, skip_mirror: bool, now_ns: int, node_over=None, pod_over=None,
-                    out: np.ndarray = None, want_drain: bool = False):
+                    out: np.ndarray = None, want_drain: bool = False, resident: bool = False):
         """utilization.Calculate of every node from the mirror's pods (ca_mirror_utilization):
         UTIL_INFO rows in position order, and with want_drain also each node's drain bits.
         node_over = (positions, UTIL_NODE rows), pod_over = (mirror pod ids, UTIL_POD rows):
         rows that replace the defaults, ids strictly ascending.  out: a caller's (page-locked)
-        result array, else a new one."""
+        result array, else a new one.  resident: from the resident pod columns
+        (ca_mirror_utilization_resident): a pod's row is its pod_over row, else the row
+        set_pod_util_rows gave it, else the default."""
         n = self.node_count()
         args, keep = abi.mirror_util_args(skip_ds, skip_mirror, now_ns, node_over, pod_over)
         if out is None:
             out = np.zeros(n, abi.UTIL_INFO_DTYPE)
         drain = np.zeros(n, np.int32) if want_drain else None
         ms = C.c_float(0)
-        _check(self.lib.ca_mirror_utilization(self.h, C.byref(args), ptr(out), ptr(drain), C.byref(ms)),
-               "ca_mirror_utilization")
+        fn = self.lib.ca_mirror_utilization_resident if resident else self.lib.ca_mirror_utilization
+        _check(fn(self.h, C.byref(args), ptr(out), ptr(drain), C.byref(ms)),
+               "ca_mirror_utilization_resident" if resident else "ca_mirror_utilization")
         del keep
         self.util_kernel_ms = ms.value
         return (out, drain) if want_drain else out
 
     def scale_down_candidates(self, skip_ds: bool, skip_mirror: bool, now_ns: int, threshold: float,
                               gpu_threshold: float, eligible=None, node_over=None,
-                              pod_over=None) -> "ScaleDownCandidates":
+                              pod_over=None, resident: bool = False) -> "ScaleDownCandidates":
         return ScaleDownCandidates(self, skip_ds, skip_mirror, now_ns, threshold, gpu_threshold, eligible,
-                                   node_over, pod_over)
+                                   node_over, pod_over, resident)
+
+    # -- resident per-pod columns: node, slot and util row per mirror pod id ----
+    def set_pod_util_rows(self, ids, rows) -> None:
+        """ca_mirror_set_pod_util_rows: UTIL_POD rows that stay with mirror pods `ids` (strictly
+        ascending) until changed; rows=None clears them back to the default rule."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        r = None if rows is None else np.ascontiguousarray(rows, dtype=abi.UTIL_POD_DTYPE)
+        if r is not None and len(r) != len(ids):
+            raise ValueError("ids and rows differ in length")
+        if r is not None and r.size == 0:
+            return
+        _check(self.lib.ca_mirror_set_pod_util_rows(self.h, ptr(ids), ptr(r), len(ids)), "ca_mirror_set_pod_util_rows")
+
+    def pod_util_rows(self, ids) -> tuple:
+        """(UTIL_POD rows, has-row flags) of mirror pods `ids`, from the host copy."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        rows = np.zeros(len(ids), abi.UTIL_POD_DTYPE)
+        has = np.zeros(len(ids), np.uint8)
+        _check(self.lib.ca_mirror_get_pod_util_rows(self.h, ptr(ids), ptr(rows), ptr(has), len(ids)),
+               "ca_mirror_get_pod_util_rows")
+        return rows, has
+
+    def pod_count(self) -> int:
+        """Mirror pod ids handed out so far (detached pods keep theirs)."""
+        n = C.c_int32(0)
+        _check(self.lib.ca_mirror_pod_count(self.h, C.byref(n)), "ca_mirror_pod_count")
+        return n.value
+
+    def pod_columns(self) -> tuple:
+        """(node, slot) per mirror pod id as the device holds them after a sync
+        (ca_mirror_fetch_pod_columns); slot is meaningful where node >= 0."""
+        n = self.pod_count()
+        node, slot = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        _check(self.lib.ca_mirror_fetch_pod_columns(self.h, ptr(node), ptr(slot), n), "ca_mirror_fetch_pod_columns")
+        return node, slot
+
+    def pod_column_stats(self) -> dict:
+        """Counters of the resident pod columns since they came into being (ca_mirror_pod_column_stats)."""
+        out = (C.c_int64 * 8)()
+        self.lib.ca_mirror_pod_column_stats(self.h, out, 8)
+        names = ["full_uploads", "staged_syncs", "entries_staged", "tail_appended", "device_reorders",
+                 "device_shifts", "rows_uploaded", "bytes_uploaded"]
+        return dict(zip(names, (int(v) for v in out)))
 
     # -- predicate checker ----------------------------------------------------
     def fits_any_node(self, table: abi.PodTable, pod: int, match=None, last_index: int = 0):
@@ -1449,7 +1505,7 @@ class ScaleDownCandidates:
     against the thresholds and the removal sweep's inputs, built inside the library."""
 
     def __init__(self, mirror: Mirror, skip_ds: bool, skip_mirror: bool, now_ns: int, threshold: float,
-                 gpu_threshold: float, eligible=None, node_over=None, pod_over=None):
+                 gpu_threshold: float, eligible=None, node_over=None, pod_over=None, resident: bool = False):
         self.m = mirror
         self.lib = mirror.lib
         self.h = None
@@ -1458,8 +1514,10 @@ class ScaleDownCandidates:
         if el is not None and len(el) != mirror.node_count():
             raise ValueError("eligible needs one byte per node")
         h = C.c_void_p()
-        _check(self.lib.ca_scale_down_candidates_create(mirror.h, C.byref(args), float(threshold), float(gpu_threshold),
-                                                        ptr(el), C.byref(h)), "ca_scale_down_candidates_create")
+        create = (self.lib.ca_scale_down_candidates_create_resident if resident
+                  else self.lib.ca_scale_down_candidates_create)
+        _check(create(mirror.h, C.byref(args), float(threshold), float(gpu_threshold), ptr(el), C.byref(h)),
+               "ca_scale_down_candidates_create_resident" if resident else "ca_scale_down_candidates_create")
         del keep
         self.h = h
         self._lists = None

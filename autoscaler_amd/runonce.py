@@ -284,16 +284,23 @@ def run(backend, util_fn, w: RunOnceWorkload, timers=None, row_zeros=_zeros, exp
     `scale_down="device"` (the device mirror only): steps 4 and 5 take utilization, the empty
     nodes, the candidates and the sweep's plan from one native.ScaleDownCandidates on the
     mirror's own state: no UtilInput, no `util_fn` call (it may be None) and no host pass over
-    the pods; "host" builds the utilization rows and the move lists in numpy."""
+    the pods; "host" builds the utilization rows and the move lists in numpy.
+    `scale_down="resident"` (the device mirror only): the device form on the mirror's resident
+    pod columns.  The drain verdicts of the running pods are set once as resident rows before
+    the timed legs (a shim classifies pods as they enter the snapshot), those of the filter's
+    placements inside the utilization leg, and no per-call override is sent."""
     if pod_groups not in ("host", "device"):
         raise ValueError('pod_groups: "host" or "device"')
-    if scale_down not in ("host", "device"):
-        raise ValueError('scale_down: "host" or "device"')
-    if scale_down == "device" and not callable(getattr(type(backend), "scale_down_candidates", None)):
-        raise TypeError('scale_down="device" needs the device mirror as backend')
+    if scale_down not in ("host", "device", "resident"):
+        raise ValueError('scale_down: "host", "device" or "resident"')
+    if scale_down != "host" and not callable(getattr(type(backend), "scale_down_candidates", None)):
+        raise TypeError(f'scale_down="{scale_down}" needs the device mirror as backend')
     f = w.filt
     r = RunOnceResult()
     clock = time.perf_counter
+    if scale_down == "resident":
+        running = np.arange(len(f.table), dtype=np.int32)        # running pod id == record index
+        backend.set_pod_util_rows(*_movable_rows(f.table.pods, running, running))
 
     # the pending pods, resident on the device for steps 1-3 (one upload; timed with step 1)
     t = clock()
@@ -366,8 +373,8 @@ def run(backend, util_fn, w: RunOnceWorkload, timers=None, row_zeros=_zeros, exp
     if ps is not None:
         ps.close()
 
-    if scale_down == "device":
-        _scale_down_on_device(backend, w, fo, r, unsched, n_eg, group_off)
+    if scale_down != "host":
+        _scale_down_on_device(backend, w, fo, r, unsched, n_eg, group_off, resident=scale_down == "resident")
         return r
 
     # 4. scale-down eligibility on the snapshot after step 1
@@ -434,14 +441,33 @@ def scale_down_overrides(w: RunOnceWorkload, fo):
     return ids[k], rows[k]
 
 
-def _scale_down_on_device(backend, w: RunOnceWorkload, fo, r: RunOnceResult, unsched, n_eg: int, group_off) -> None:
-    """Steps 4 and 5 of run() from one ScaleDownCandidates handle and its plan."""
+def _movable_rows(pods, rec, ids):
+    """(ids, UTIL_POD rows) of the mirror pods flagged CA_POD_DAEMONSET, pods[rec[k]] being the
+    record of mirror pod ids[k] (ascending): the synthetic loop's drain verdict, "movable", with
+    the default requests.  Only the flags column is gathered for every pod."""
+    ds = np.nonzero(pods["flags"][rec] & abi.CA_POD_DAEMONSET)[0]
+    at = rec[ds]
+    rows = np.zeros(len(ds), abi.UTIL_POD_DTYPE)
+    rows["req_milli"][:, 0] = pods["score_milli_cpu"][at]
+    rows["req_milli"][:, 1] = pods["score_memory"][at] * 1000
+    rows["flags"] = abi.CA_UPOD_MOVABLE
+    return np.ascontiguousarray(ids[ds], dtype=np.int32), rows
+
+
+def _scale_down_on_device(backend, w: RunOnceWorkload, fo, r: RunOnceResult, unsched, n_eg: int, group_off,
+                          resident: bool = False) -> None:
+    """Steps 4 and 5 of run() from one ScaleDownCandidates handle and its plan.  resident: on the
+    resident pod columns; only the rows of this loop's placements are sent."""
     f = w.filt
     clock = time.perf_counter
-    over = scale_down_overrides(w, fo)
+    over = None if resident else scale_down_overrides(w, fo)
     # 4. utilization, classes and lists from the mirror's state after step 1
     t = clock()
-    sd = backend.scale_down_candidates(False, False, w.now_ns, UTIL_THRESHOLD, UTIL_THRESHOLD, pod_over=over)
+    if resident:
+        placed = np.nonzero(fo.node >= 0)[0]                      # (pod ids ascend with the placement order)
+        backend.set_pod_util_rows(*_movable_rows(f.pending.pods, f.order[placed], fo.pod_id[placed]))
+    sd = backend.scale_down_candidates(False, False, w.now_ns, UTIL_THRESHOLD, UTIL_THRESHOLD, pod_over=over,
+                                       resident=resident)
     ls = sd.fetch()
     r.ms["utilization"] = (clock() - t) * 1e3
     r.util, r.empty, r.candidates = ls.info, ls.empty, ls.cand

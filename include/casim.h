@@ -911,6 +911,50 @@ int ca_scale_down_candidates_destroy(ca_scale_down_candidates* h);
 int ca_removal_plan_create_candidates(const ca_scale_down_candidates* h, const int32_t* nodes, int32_t n,
         const uint8_t* dest_mask, ca_removal_plan** out);
 
+/* ---- scale-down from resident pod columns ---------------------------------------
+ * Three per-pod columns kept on the device, indexed by mirror pod id: the pod's node
+ * (PodRow.node, -1 on no node), its slot in the node's NodeInfo.Pods list, and a ca_util_pod the
+ * caller set for it with a has-row flag.  They come into being at the first call below, start
+ * with one full upload, follow every mutation of the mirror (adds, removals, fork / revert,
+ * placements, the planner's moves, node removal, reorder) and are dropped by ca_mirror_clear,
+ * resident rows included; a mirror that never calls these pays nothing.  The host rows stay
+ * authoritative: the device copy is brought up to date before a kernel reads it, ids past the
+ * synced count as one contiguous append, changed ids as (id, node, slot) entries behind a
+ * scatter, more than max(1024, n_pods / 4) of them as a full upload.
+ *  util rows    attributes of a pod id, not journaled (a row set inside a fork survives the
+ *               revert; a row on a detached pod is kept and applies when a revert re-attaches
+ *               it).  The copy the planner commits inherits its source's row; pods that enter
+ *               through ca_mirror_add_pods or FilterOutSchedulable start without one.
+ *  set / get    pod_ids strictly ascending and in range, else CA_EINVAL and nothing changes;
+ *               rows NULL clears the ids back to the default rule.  get answers from the host
+ *               copy (rows and has_row may each be NULL).
+ *  _resident    ca_mirror_utilization / ca_scale_down_candidates_create reading the columns: no
+ *               per-call pass over the pod records.  Same arguments, checks, error codes and
+ *               "outputs untouched" guarantees.  A pod's row is its per-call override, else its
+ *               resident row, else the default.  The handle is the same type; its move lists are
+ *               built on the device, timings[2] is the host time of the column sync and
+ *               timings[3] the device time of the move-list kernels.  CA_EDEVICE ("pod columns
+ *               out of sync", no handle) when a slot lies outside its node's list: nothing is
+ *               written there.
+ *  fetch        syncs, then copies the device columns out (n_pods = the mirror's pod ids,
+ *               ca_mirror_pod_count, else CA_EINVAL); slot is meaningful where node >= 0.
+ *  pod_count    mirror pod ids handed out so far (detached pods keep theirs; 0 after
+ *               ca_mirror_clear): the length of every per-pod array of this header.
+ *  stats        since the columns came into being: [0] full uploads, [1] staged syncs,
+ *               [2] entries staged in them, [3] tail entries appended, [4] reorders done on the
+ *               device, [5] node shifts done on the device (a node removal and its revert mark
+ *               a full upload instead), [6] util rows uploaded, [7] bytes copied to the device
+ *               for the columns; returns 8. */
+int ca_mirror_set_pod_util_rows(ca_mirror* m, const int32_t* pod_ids, const ca_util_pod* rows, int32_t n);
+int ca_mirror_get_pod_util_rows(ca_mirror* m, const int32_t* pod_ids, ca_util_pod* rows, uint8_t* has_row, int32_t n);
+int ca_mirror_utilization_resident(ca_mirror* m, const ca_mirror_util_args* a, ca_util_info* out,
+                                   int32_t* out_drain, float* kernel_ms);
+int ca_scale_down_candidates_create_resident(ca_mirror* m, const ca_mirror_util_args* a, double threshold,
+        double gpu_threshold, const uint8_t* eligible, ca_scale_down_candidates** out);
+int ca_mirror_fetch_pod_columns(ca_mirror* m, int32_t* node, int32_t* slot, int32_t n_pods);
+int ca_mirror_pod_count(const ca_mirror* m, int32_t* out);
+int ca_mirror_pod_column_stats(const ca_mirror* m, int64_t* out, int32_t cap);
+
 /* ---- multi-GPU ---------------------------------------------
  * One mirror per device (ca_mirror_create(device)), kept identical by the caller: every
  * snapshot change (add/remove nodes and pods, fork/revert/commit, hints) is applied to
