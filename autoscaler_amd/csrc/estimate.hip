@@ -18,7 +18,8 @@
 //                                        lists never change after creation.
 //   st  (heavy groups)   k_run_table     class ranks, the plan's counts by rank, each rank's
 //                                        first stream position, the class's stream record
-//                                        against the template.
+//                                        against the template, its requests and their
+//                                        reciprocals in float64.
 //                        k_ffd_chain     one 4-wave workgroup per group: the sequential
 //                                        First-Fit-Decreasing loop (per pod, or per run of
 //                                        identical pods in closed form) with the new-node
@@ -26,7 +27,10 @@
 //                                        to LDS in its prologue); pushes 16384-output tickets.
 //                                        (CASIM_TABLE_CHAIN=0, or a table too large for LDS:
 //                                        k_emit_runs writes run heads and stream windows
-//                                        first and the chain reads those.)
+//                                        first and the chain reads those.)  Rows in LDS, no
+//                                        ports / extended resources / node ordinals, groups
+//                                        <= 2^20 pods, quantities < 2^53: the lean
+//                                        instantiation (CASIM_LEAN_CHAIN=0: the generic one).
 //   st2 (light groups)   the same kernels for the groups outside the heavy set.
 //   pub_stream           k_publish       claims tickets in completion order and writes the
 //                                        scheduled pods (Go-order ids) into the caller's
@@ -704,6 +708,12 @@ __global__ void __launch_bounds__(256) k_cls_hist(const GroupMeta* __restrict__ 
         if (h[c] > 0) atomicAdd(&out[c], h[c]);
 }
 
+// A request and its reciprocal in float64, for the copy counts of a run (run_div below;
+// k_run_table writes the same two per rank).  req == 0: rcp = +inf, the quotient inf (NaN
+// for free == 0) and fmin(., cap) gives cap — a zero request passes whenever free >= 0.
+__device__ inline double run_req(int64_t req) { return (double)req; }
+__device__ inline double run_rcp(int64_t req) { return req > 0 ? 1.0 / (double)req : __builtin_inf(); }
+
 __device__ inline int32_t run_rank(const int32_t* __restrict__ st, int32_t U, int32_t i) {
     int32_t lo = 0, hi = U;                  // the last r with st[r] <= i (st[U] is never read)
     while (hi - lo > 1) {
@@ -723,9 +733,12 @@ __global__ void __launch_bounds__(1024) k_run_table(const GroupMeta* __restrict_
                                                    const ca_selector_req* __restrict__ reqs, int32_t* __restrict__ rstart,
                                                    StreamPod* __restrict__ rsp, uint32_t* __restrict__ group_unsup,
                                                    const int32_t* __restrict__ gmap,
-                                                   int32_t* __restrict__ lin, uint8_t* __restrict__ need, int32_t lin0) {
+                                                   int32_t* __restrict__ lin, uint8_t* __restrict__ need, int32_t lin0,
+                                                   double* __restrict__ rdiv) {
     // lin != null: round 1 without k_round_init — the group's lastIndex input, need flag and
     // unsupported flag are set here (stored, not or-ed)
+    // rdiv != null: rdiv[g][r][0..6) the rank's requests and their reciprocals in float64
+    // (run_div's values, one thread per class here instead of once per run on the chain)
     __shared__ int32_t cnt[CLS_MAX];
     __shared__ uint32_t s_unsup;
     __shared__ int32_t rc[CLS_MAX];
@@ -805,6 +818,14 @@ __global__ void __launch_bounds__(1024) k_run_table(const GroupMeta* __restrict_
         sp.pod = cls_rep[c];
         sp.flags = sf | (batchable(p, sf) ? SF_BATCH : 0u);
         rsp[(size_t)gi * U + cr[c]] = sp;
+        if (rdiv) {
+            double* d = rdiv + ((size_t)gi * U + cr[c]) * 6;
+            const int64_t req[3] = {p.cpu, p.mem, p.eph};
+            for (int i = 0; i < 3; i++) {
+                d[i] = run_req(req[i]);
+                d[3 + i] = run_rcp(req[i]);
+            }
+        }
         unsup |= sf & SF_UNSUP;
     }
     if (unsup) atomicOr(&s_unsup, 1u);
@@ -1286,15 +1307,21 @@ __global__ void __launch_bounds__(256) k_emit_bucket(const GroupMeta* __restrict
 
 // 4. the First-Fit-Decreasing chain -------------------------------------------
 #ifdef CASIM_PROF   // section cycle counters of k_ffd_chain (profiling build only)
-constexpr int NPROF = 15;   // + [12] loop top (window moves, head reads), [13] epilogue, [14] before the loop
+constexpr int NPROF = 23;   // + [12] loop top (window moves, head reads), [13] epilogue, [14] before the loop
+// [15..16] blocks over all row passes, of the wave that sent most to the quotients: rows read,
+// admitted to the float64 quotients ([17] that wave); [18..19] the row pass split: rows (with
+// the wave reductions the compiler schedules ahead of the clock), cross-wave exchange;
+// [20..22] an opening: the template's copy count, row writes and barrier, evals and segment
 __device__ unsigned long long g_chain_prof[1024][NPROF];
 #define PROF_T(v) const uint64_t v = clock64()
 #define PROF_ADD(i, t) prof[i] += clock64() - (t)
 #define PROF_INC(i) prof[i]++
+#define PROF_ADDN(i, n) prof[i] += (n)
 #else
 #define PROF_T(v) (void)0
 #define PROF_ADD(i, t) (void)0
 #define PROF_INC(i) (void)0
+#define PROF_ADDN(i, n) (void)0
 #endif
 __device__ inline int64_t rl64(int64_t v, int lane) {
     const uint64_t u = (uint64_t)v;
@@ -1513,10 +1540,8 @@ __device__ inline RunDiv run_div(int64_t pcpu, int64_t pmem, int64_t peph, int64
     d.f64 = bound < E53 && pcpu < E53 && pmem < E53 && peph < E53;
     const int64_t req[3] = {pcpu, pmem, peph};
     for (int i = 0; i < 3; i++) {
-        d.reqd[i] = (double)req[i];
-        // req == 0: rcp = +inf, the quotient inf (NaN for free == 0) and fmin(., cap)
-        // gives cap — a zero request passes whenever free >= 0
-        d.rcpd[i] = req[i] > 0 ? 1.0 / d.reqd[i] : __builtin_inf();
+        d.reqd[i] = run_req(req[i]);
+        d.rcpd[i] = run_rcp(req[i]);
     }
     return d;
 }
@@ -1533,6 +1558,9 @@ __device__ inline int32_t dim_copies_f64(int64_t free_, double rd, double rcpd, 
     q -= (t < 0.0) ? 1.0 : 0.0;
     return free_ < 0 ? 0 : (int32_t)q;
 }
+// SREQ: the zero-request tests read the scalar integer requests (the lean chain's float64
+// values come from LDS in vector registers; the test is the same one)
+template <bool SREQ = false>
 __device__ inline int32_t rec_copies_run(const NodeRec& r, const RunDiv& d, bool zero, int32_t cap,
                                          int64_t pcpu, int64_t pmem, int64_t peph) {
     if (!d.f64) return rec_copies(r, pcpu, pmem, peph, zero, cap);     // uniform
@@ -1541,9 +1569,11 @@ __device__ inline int32_t rec_copies_run(const NodeRec& r, const RunDiv& d, bool
         // independent per-dimension quotients (capped at the same c, min taken after);
         // a zero request only needs free >= 0 (uniform skip of the division)
         const int32_t cp = max(c, 1);
-        const int32_t q0 = d.reqd[0] != 0.0 ? dim_copies_f64(r.cpu, d.reqd[0], d.rcpd[0], cp) : (r.cpu < 0 ? 0 : cp);
-        const int32_t q1 = d.reqd[1] != 0.0 ? dim_copies_f64(r.mem, d.reqd[1], d.rcpd[1], cp) : (r.mem < 0 ? 0 : cp);
-        const int32_t q2 = d.reqd[2] != 0.0 ? dim_copies_f64(r.eph, d.reqd[2], d.rcpd[2], cp) : (r.eph < 0 ? 0 : cp);
+        const bool n0 = SREQ ? pcpu != 0 : d.reqd[0] != 0.0, n1 = SREQ ? pmem != 0 : d.reqd[1] != 0.0,
+                   n2 = SREQ ? peph != 0 : d.reqd[2] != 0.0;
+        const int32_t q0 = n0 ? dim_copies_f64(r.cpu, d.reqd[0], d.rcpd[0], cp) : (r.cpu < 0 ? 0 : cp);
+        const int32_t q1 = n1 ? dim_copies_f64(r.mem, d.reqd[1], d.rcpd[1], cp) : (r.mem < 0 ? 0 : cp);
+        const int32_t q2 = n2 ? dim_copies_f64(r.eph, d.reqd[2], d.rcpd[2], cp) : (r.eph < 0 ? 0 : cp);
         c = min(c, min(q0, min(q1, q2)));
     }
     return c;
@@ -1942,7 +1972,14 @@ __global__ void __launch_bounds__(256) k_publish(const GroupMeta* __restrict__ g
 // record, first position and end come from LDS, `stream` and `heads` are never read and
 // the loop issues no global load (k_emit_runs is not launched).  A non-batchable rank is a
 // run of `count` single pods of one record.
-template <bool GROWS, bool PS, bool TB>
+// LEAN (with TB, rows in LDS, no PS): the headline's case — no node ordinals wanted, every
+// group of at most 2^20 pods, every template free value and request below 2^53 (a plan
+// fact).  Such a call never takes the integer rec_copies path, the rem > 2^20 path or the
+// placement list, so they are not instantiated, and a run's float64 requests and reciprocals
+// come from the table (rdiv, k_run_table) instead of three divisions and the conversions at
+// its entry.  The loop is otherwise the generic one; every other call runs the generic
+// instantiations.
+template <bool GROWS, bool PS, bool TB, bool LEAN = false>
 __global__ void __launch_bounds__(CT) k_ffd_chain(
     const GroupMeta* __restrict__ groups, const StreamPod* __restrict__ stream, const uint64_t* __restrict__ heads,
     const ca_template* __restrict__ tmpls, const ca_pod_spec* __restrict__ specs, const PodHot* __restrict__ ph,
@@ -1953,7 +1990,8 @@ __global__ void __launch_bounds__(CT) k_ffd_chain(
     ChainOut* __restrict__ outs, const int32_t* __restrict__ gmap, unsigned char* __restrict__ gslab,
     const int64_t* __restrict__ slab_off, const int32_t* __restrict__ gkcap, int32_t pos_out,
     ChainOut* __restrict__ hout, int32_t* __restrict__ hflags, const int32_t* __restrict__ rstart,
-    const StreamPod* __restrict__ rsp, int32_t U, int32_t tab_off) {
+    const StreamPod* __restrict__ rsp, int32_t U, int32_t tab_off, const double* __restrict__ rdiv) {
+    static_assert(!LEAN || (TB && !GROWS && !PS), "the lean chain: run table, rows in LDS, no ports or scalars");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int g = GSEL(blockIdx.x);
     // GROWS: the group's rows live in its own HBM slab (kcap = the group's pod count, for an
@@ -1974,7 +2012,7 @@ __global__ void __launch_bounds__(CT) k_ffd_chain(
 #endif
     uint32_t n_single = 0;
 #ifdef CASIM_PROF
-    uint64_t prof[NPROF] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    uint64_t prof[NPROF] = {};
 #endif
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -2023,7 +2061,7 @@ __global__ void __launch_bounds__(CT) k_ffd_chain(
     Seg* gseg = segs + gm.off;
     int32_t nseg = 0;
     int32_t* so_pod = sched_pod + gm.off;
-    int32_t* so_node = sched_node ? sched_node + gm.off : nullptr;
+    int32_t* const so_node = (!LEAN && sched_node) ? sched_node + gm.off : nullptr;
     // Stream double buffer: lane l holds entry (wbase + l) in `cur` and (wbase + 64 + l)
     // in `nxt`.  Single-pod placements are kept in the lane of their stream position and
     // stored when the window moves on, so no step waits on a store (vmcnt counts both).
@@ -2049,19 +2087,26 @@ __global__ void __launch_bounds__(CT) k_ffd_chain(
     // loop keeps the next run's record (t_nrec) and the entry after it (t_npair: the next
     // run's end, the rank of the run after) in registers, read from LDS when the run before
     // started, so taking a run waits for nothing.
+    // LEAN: TDIV[r] behind TREC — the rank's three requests and their reciprocals in float64
+    // (48 B), kept in registers one run ahead like the record (t_ndiv).
+    struct RankDiv { double v[6]; };
     StreamPod* const TREC = reinterpret_cast<StreamPod*>(smem_raw + tab_off);
-    int2* const TRUN = reinterpret_cast<int2*>(TREC + (TB ? U : 0));
+    RankDiv* const TDIV = reinterpret_cast<RankDiv*>(TREC + (TB ? U : 0));
+    int2* const TRUN = reinterpret_cast<int2*>(TDIV + (LEAN ? U : 0));
     int32_t* const TST = reinterpret_cast<int32_t*>(TRUN + (TB ? U + 1 : 0));
     int32_t t_next = 0, t_end = 0, n_runs = 0;     // the next run of the list; the current run's end
     StreamPod t_nrec = {};
+    RankDiv t_ndiv = {}, t_div = {};
     int2 t_npair = make_int2(0, 0);
     if (TB) {
         const StreamPod* rp = rsp + (size_t)g * U;
+        const RankDiv* dp = LEAN ? reinterpret_cast<const RankDiv*>(rdiv) + (size_t)g * U : nullptr;
         for (int32_t r = tid; r < U; r += CT) {
             // (the first CT ranks' starts were requested at the kernel's entry)
             const int32_t a = r < CT ? t_a0 : t_rs[r], b = r < CT ? t_b0 : t_rs[r + 1];
             TST[r] = a;
             if (b > a) TREC[r] = rp[r];        // (an absent rank's record was never written)
+            if (LEAN && b > a) TDIV[r] = dp[r];
         }
         if (tid == 0) TST[U] = P;
         cbar<GROWS>();
@@ -2085,6 +2130,7 @@ __global__ void __launch_bounds__(CT) k_ffd_chain(
         if (tid == 0) TRUN[n_runs] = make_int2(0, P);
         cbar<GROWS>();
         t_nrec = TREC[TRUN[0].x];
+        if (LEAN) t_ndiv = TDIV[TRUN[0].x];
         t_npair = TRUN[min(1, n_runs)];
     }
 
@@ -2168,6 +2214,7 @@ __global__ void __launch_bounds__(CT) k_ffd_chain(
             cur.flags |= SF_HEAD;           // a batchable run is entered at its head only
             t_end = rl32(t_npair.y, 0);
             t_next++;
+            if (LEAN) { t_div = t_ndiv; t_ndiv = TDIV[t_npair.x]; }
             t_nrec = TREC[t_npair.x];       // the run after: in flight behind this run's LDS work
             t_npair = TRUN[min(t_next + 1, n_runs)];
         }
@@ -2177,12 +2224,16 @@ __global__ void __launch_bounds__(CT) k_ffd_chain(
         const uint32_t sf = (uint32_t)rl32((int32_t)cur.flags, rsl);
         const bool zero = (sf & SF_ZERO) != 0;
 #ifdef CASIM_PROF
-        __builtin_amdgcn_s_waitcnt(0);       // (profiling: the head's loads land here, not in the run)
+        // (profiling: the stream chain's head loads land here, not in the run; the run-table
+        // chain issues no load here and is timed without the drain, so its sections add up)
+        if (!TB) __builtin_amdgcn_s_waitcnt(0);
 #endif
         PROF_ADD(12, t_top);
 
         // ---------------- a run of identical resource-only pods ----------------
-        if (batch_runs && (sf & (SF_BATCH | SF_HEAD)) == (SF_BATCH | SF_HEAD)) {
+        // (LEAN: runs are the loop's body; the per-pod path below is laid out behind it)
+        const bool is_run = batch_runs && (sf & (SF_BATCH | SF_HEAD)) == (SF_BATCH | SF_HEAD);
+        if (LEAN ? __builtin_expect(is_run, true) : is_run) {
             PROF_T(t_re);
             PROF_T(t_run);
             const int32_t e = TB ? t_end : run_end_pf(hm, pos, P, lane, pf_hc, pf_hw);
@@ -2206,7 +2257,13 @@ __global__ void __launch_bounds__(CT) k_ffd_chain(
                 const uint64_t kev = (sf & SF_EVAL) ? 1u : 0u;
                 // the pod's reciprocals, once per run (copy counts of every row, the last
                 // row and the template: fast path while the cap is <= 2^20)
-                const RunDiv dv = run_div(pcpu, pmem, peph, max(trec.cpu, max(trec.mem, trec.eph)));
+                RunDiv dv;
+                if (LEAN) {     // from the table: no division and no conversion at a run's entry
+                    for (int i = 0; i < 3; i++) { dv.reqd[i] = t_div.v[i]; dv.rcpd[i] = t_div.v[3 + i]; }
+                    dv.f64 = true;
+                } else {
+                    dv = run_div(pcpu, pmem, peph, max(trec.cpu, max(trec.mem, trec.eph)));
+                }
                 int32_t done = 0;
                 bool exhausted = false;          // every row but last_node has no room left
                 PROF_ADD(8, t_pro);
@@ -2232,8 +2289,9 @@ __global__ void __launch_bounds__(CT) k_ffd_chain(
                         if (exhausted) {
                             PROF_T(t_ex);
                             const NodeRec rl_ = R[last_node];
-                            const int32_t c = rem <= (1 << 20) ? rec_copies_run(rl_, dv, zero, rem, pcpu, pmem, peph)
-                                                               : rec_copies(rl_, pcpu, pmem, peph, zero, rem);
+                            const int32_t c = LEAN ? rec_copies_run<true>(rl_, dv, zero, rem, pcpu, pmem, peph)
+                                              : rem <= (1 << 20) ? rec_copies_run(rl_, dv, zero, rem, pcpu, pmem, peph)
+                                                                 : rec_copies(rl_, pcpu, pmem, peph, zero, rem);
                             cbar<GROWS>();    // every wave has read the row before it changes
                             if (c > 0) { one = last_node; n_one = c; nalive = 1; }
                             PROF_ADD(10, t_ex);
@@ -2258,7 +2316,7 @@ __global__ void __launch_bounds__(CT) k_ffd_chain(
                                 if (m) a1_w = b + hibit(m);
                                 return in ? c : 0;
                             };
-                            const bool fast = rem <= (1 << 20);
+                            const bool fast = LEAN || rem <= (1 << 20);
                             if (fast) {
                                 // Block skip: a row has room for a copy iff the pod fits it
                                 // (rec_fits: compares only), so the float64 copy counts run
@@ -2273,6 +2331,8 @@ __global__ void __launch_bounds__(CT) k_ffd_chain(
                                     const NodeRec r0 = R[in0 ? j : 0], r1 = R[in1 ? j + 64 : 0];
                                     const uint64_t f0 = __ballot(in0 && (all || rec_fits(r0, pcpu, pmem, peph, zero)));
                                     const uint64_t f1 = __ballot(in1 && (all || rec_fits(r1, pcpu, pmem, peph, zero)));
+                                    PROF_ADDN(15, (b < hi) + (b + 64 < hi));
+                                    PROF_ADDN(16, (f0 != 0) + (f1 != 0));
                                     if (f0) {
                                         adm_w |= 1ull << ((b - lo) >> 6);
                                         s32 += acc(b, rec_copies_run(r0, dv, zero, rem, pcpu, pmem, peph), in0);
@@ -2294,11 +2354,14 @@ __global__ void __launch_bounds__(CT) k_ffd_chain(
                                     s64 += acc(b, rec_copies(R[in ? j : 0], pcpu, pmem, peph, zero, rem), in);
                                 }
                             }
+                            PROF_ADD(18, t_ca);
+                            PROF_T(t_wr);
                             int64_t x[RED_N];          // S, rows with room, last such row, fewest copies, rows < j0
                             x[0] = fast ? (int64_t)__ockl_wfred_add_i32(s32) : wave_sum64(s64);
                             x[1] = na_w; x[2] = a1_w; x[3] = wave_min32(cm); x[4] = lt_w;
                             constexpr int OPS[RED_N] = {R_SUM, R_SUM, R_MAX, R_MIN, R_SUM};
                             blk_xchg5<GROWS>(cred, par, wv, lane, x, OPS);     // + CAPA visible
+                            PROF_ADD(19, t_wr);
                             S = x[0];
                             nalive = (int32_t)x[1];
                             lv_cmin = x[3];
@@ -2552,8 +2615,11 @@ __global__ void __launch_bounds__(CT) k_ffd_chain(
                     // and takes one limiter grant.  Closed form over n_open nodes.
                     PROF_T(t_op);
                     const int32_t ct = !(sf & SF_FA_OK) ? 1
+                                       : LEAN ? rec_copies_run<true>(trec, dv, zero, rem2, pcpu, pmem, peph)
                                        : rem2 <= (1 << 20) ? rec_copies_run(trec, dv, zero, rem2, pcpu, pmem, peph)
                                                            : rec_copies(trec, pcpu, pmem, peph, zero, rem2);
+                    PROF_ADD(20, t_op);
+                    PROF_T(t_ow);
                     int32_t n_open = (rem2 + ct - 1) / ct;
                     if (max_nodes > 0) n_open = min(n_open, 1 + (max_nodes - granted));
                     n_open = min(n_open, kcap - k);
@@ -2585,6 +2651,8 @@ __global__ void __launch_bounds__(CT) k_ffd_chain(
                         }
                     }
                     cbar<GROWS>();                                                  // new rows visible
+                    PROF_ADD(21, t_ow);
+                    PROF_T(t_oe);
                     evals += open_evals(n_open, ct, placed2, k0, j00, kev, (sf & SF_CP_EVAL) != 0);
                     if (so_node) for (int32_t t = tid; t < placed2; t += CT) so_node[nsched + t] = k0 + t / ct;
                     if (tid == 0 && placed2 > 0) gseg[nseg] = Seg{nsched, pos + done, placed2, 0};
@@ -2600,6 +2668,7 @@ __global__ void __launch_bounds__(CT) k_ffd_chain(
                     nsched += placed2;
                     done += placed2;
                     progress();
+                    PROF_ADD(22, t_oe);
                     PROF_ADD(4, t_op);
                 }
                 pos = e;
@@ -2752,6 +2821,10 @@ __global__ void __launch_bounds__(CT) k_ffd_chain(
         so_pod[out_idx] = (TB || pos_out) ? wbase + lane : cur.pod;
         if (so_node) so_node[out_idx] = out_node;
     }
+#ifdef CASIM_PROF
+    __shared__ unsigned long long s_blk[CW][2];     // each wave's block counters, for the busiest one
+    if (lane == 0) { s_blk[wv][0] = prof[15]; s_blk[wv][1] = prof[16]; }
+#endif
     // newNodesWithPods
     cbar<GROWS>();
     int64_t cnt = 0, z0 = 0, z1 = 0;
@@ -2789,6 +2862,9 @@ __global__ void __launch_bounds__(CT) k_ffd_chain(
 #ifdef CASIM_PROF
         prof[13] = clock64() - t_epi;
         prof[5] = clock64() - t_cyc0;
+        int bw = 0;
+        for (int w = 1; w < CW; w++) if (s_blk[w][1] > s_blk[bw][1]) bw = w;
+        prof[15] = s_blk[bw][0]; prof[16] = s_blk[bw][1]; prof[17] = (unsigned long long)bw;
         if (g < 1024) for (int i = 0; i < NPROF; i++) g_chain_prof[g][i] = prof[i];
 #endif
     }
@@ -2882,6 +2958,10 @@ struct ca_estimate_plan {
     // permutation; d_ids_ready: per group, the run epoch whose ids are final there)
     DevBuf d_sortC, d_ids_ready, d_spod_go, d_crank2;
     DevBuf d_rstart, d_rsp;        // decoupled: per group, each rank's first stream position and record
+    DevBuf d_rdiv;                 // ... and its requests and their reciprocals in float64 (6 per rank: the lean chain)
+    // every template's free values and every pod's requests are below 2^53: float64 copy
+    // counts are exact for every run of this plan (a condition of the lean chain)
+    bool f64_exact = false;
     DevBuf d_item_cls;             // bucket path: the score class of every (group, pod) item, uploaded with the lists
     // ... with uniform classes: [G][n_cls] items of each class in each list (k_cls_hist), in
     // the tail of d_item_cls (one allocation: a hipMalloc costs more than the histogram)
@@ -2922,6 +3002,7 @@ struct ca_estimate_plan {
     bool pub_clean = false;
     int32_t ran_decoupled = 0;     // last run took the decoupled Go order
     int32_t ran_table_chain = 0;   // ... and its chains walked the run table (k_ffd_chain<.., TB>)
+    int32_t ran_lean_chain = 0;    // ... with the lean instantiation (k_ffd_chain<.., TB, LEAN>)
     bool phase_events = true;      // record the per-phase timing events (ca_estimate_plan_set_phase_timing)
     std::vector<uint64_t> diag;     // per group: chain ticks (100 MHz) | single-pod steps << 32
     std::vector<uint8_t> grp_succ;  // last run, per group: a FitsAnyNode call succeeded (moved lastIndex)
@@ -3464,6 +3545,7 @@ int plan_prepare(ca_estimate_plan* p, ca_mirror* m, const ca_podset* s, const in
     p->n_tiles = 0;
     p->n_hist = 0;
     p->max_rtiles = 0;
+    p->f64_exact = s->req_below_2p53;
     {
         const char* e = knob_env("CASIM_SORT");      // "merge" forces the comparison sort (tests run both)
         p->bucket = s->n_cls <= CLS_MAX && !(e && strcmp(e, "merge") == 0);
@@ -3477,6 +3559,7 @@ int plan_prepare(ca_estimate_plan* p, ca_mirror* m, const ca_podset* s, const in
         gm.tmem = wsub(t.node.alloc_memory, t.used_memory);
         gm.teph = wsub(t.node.alloc_ephemeral, t.used_ephemeral);
         gm.tpods = clamp_i32(t.node.alloc_pods - t.used_pods);
+        if (std::max(gm.tcpu, std::max(gm.tmem, gm.teph)) >= (1ll << 53)) p->f64_exact = false;   // (run_div's bound)
         gm.off = group_off[g];
         gm.count = c;
         gm.tmpl = g;
@@ -3594,6 +3677,8 @@ int plan_prepare(ca_estimate_plan* p, ca_mirror* m, const ca_podset* s, const in
         if ((rc = p->d_rstart.reserve(sizeof(int32_t) * (size_t)std::max(G, 1) * (size_t)(s->n_cls + 1))) != CA_OK)
             return rc;
         if ((rc = p->d_rsp.reserve(sizeof(StreamPod) * (size_t)std::max(G, 1) * (size_t)std::max(s->n_cls, 1))) != CA_OK)
+            return rc;
+        if ((rc = p->d_rdiv.reserve(sizeof(double) * 6 * (size_t)std::max(G, 1) * (size_t)std::max(s->n_cls, 1))) != CA_OK)
             return rc;
     }
     if (G) CA_HIP_CHECK(hipMemcpyAsync(p->d_meta.ptr, p->h_meta.data(), sizeof(GroupMeta) * G, hipMemcpyHostToDevice, st));
@@ -3747,18 +3832,20 @@ int32_t pub_blocks(bool decoupled, bool table_chain) {
 // The run-table chain's table of a podset with U score classes (k_ffd_chain<.., TB>): a
 // 32-B record and a first position per rank, and the list of (rank, first position) of
 // the ranks that start a run.
-size_t chain_table_bytes(int32_t U) {
-    return (sizeof(StreamPod) * (size_t)U + (sizeof(int2) + sizeof(int32_t)) * ((size_t)U + 1) + 15) & ~(size_t)15;
+// lean: and the rank's float64 requests and reciprocals (48 B) behind its record.
+size_t chain_table_bytes(int32_t U, bool lean = false) {
+    return ((sizeof(StreamPod) + (lean ? 6 * sizeof(double) : 0)) * (size_t)U +
+            (sizeof(int2) + sizeof(int32_t)) * ((size_t)U + 1) + 15) & ~(size_t)15;
 }
 // table_ranks >= 0: with the run table of that many classes behind the rows (which start
 // 16-byte aligned: the table's offset is the size without it)
-size_t chain_lds_bytes(int32_t kcap, bool use_ports, bool use_scalar, int32_t table_ranks = -1) {
+size_t chain_lds_bytes(int32_t kcap, bool use_ports, bool use_scalar, int32_t table_ranks = -1, bool lean = false) {
     const size_t nb = (size_t)((kcap + 63) >> 6);
     size_t b = 32 * ((size_t)kcap + nb) + 8 * (size_t)kcap;   // rows, summaries, CAPA + ALIVE
     if (use_ports) b += 8 * CA_PORT_WORDS * (size_t)kcap;
     if (use_scalar) b += 8 * CA_MAX_SCALAR * (size_t)kcap;
     b = (b + 15) & ~(size_t)15;
-    if (table_ranks >= 0) b += chain_table_bytes(table_ranks);
+    if (table_ranks >= 0) b += chain_table_bytes(table_ranks, lean);
     return b;
 }
 
@@ -3932,7 +4019,20 @@ int plan_run(ca_estimate_plan* p, const ca_limiter* lim, int32_t* last_index, ca
         if (with_table + sizeof(ChainRed) > 160 * 1024) { table_chain = false; tab_off = 0; }
         else lds = with_table;
     }
+    // The lean chain (k_ffd_chain<.., TB, LEAN>): the run-table chain with rows in LDS, no
+    // ports or scalars, no node ordinals wanted, groups of at most 2^20 pods and float64-exact
+    // quantities (a plan fact); its table carries 48 B more per class, and one that no
+    // longer fits keeps the generic kernel.  CASIM_LEAN_CHAIN=0: the generic kernel (tests, A/B).
+    bool lean_chain = table_chain && !grows && !p->use_ports && !p->use_scalar && !sched_node &&
+                      p->max_count <= (1 << 20) && p->f64_exact && (kcap + 63) / 64 <= 64 &&
+                      !(knob_env("CASIM_LEAN_CHAIN") && atoi(knob_env("CASIM_LEAN_CHAIN")) == 0);
+    if (lean_chain) {
+        const size_t with_lean = chain_lds_bytes(kcap, false, false, p->s->n_cls, true);
+        if (with_lean + sizeof(ChainRed) > 160 * 1024) lean_chain = false;
+        else lds = with_lean;
+    }
     p->ran_table_chain = table_chain ? 1 : 0;
+    p->ran_lean_chain = lean_chain ? 1 : 0;
     const int32_t lin0 = *last_index;
     if (publish) p->pub_clean = false;        // set again once this run's publishers all finished clean
     bool pub_gave_up = false;
@@ -4036,7 +4136,8 @@ int plan_run(ca_estimate_plan* p, const ca_limiter* lim, int32_t* last_index, ca
                                    p->d_tmpl.as<ca_template>(), p->s->t.hot.as<PodHot>(), p->s->t.spec.as<ca_pod_spec>(),
                                    p->s->t.terms.as<ca_selector_term>(), p->s->t.reqs.as<ca_selector_req>(),
                                    p->d_rstart.as<int32_t>(), p->d_rsp.as<StreamPod>(), p->d_unsup.as<uint32_t>(), gm,
-                                   fast_init ? p->d_lin.as<int32_t>() : nullptr, p->d_need.as<uint8_t>(), lin0);
+                                   fast_init ? p->d_lin.as<int32_t>() : nullptr, p->d_need.as<uint8_t>(), lin0,
+                                   p->d_rdiv.as<double>());
                 CA_HIP_CHECK(hipGetLastError());
                 if (!table_chain) {     // (the run-table chain reads the table, not the stream)
                     hipLaunchKernelGGL(k_emit_runs, dim3(blocks, ng), dim3(256), 0, ss, p->d_meta.as<GroupMeta>(),
@@ -4204,6 +4305,7 @@ int plan_run(ca_estimate_plan* p, const ca_limiter* lim, int32_t* last_index, ca
         if (p->phase_events) CA_HIP_CHECK(hipEventRecord(p->ev[ca_estimate_plan::EV_CHAIN0], st));
         const bool ps = p->use_ports || p->use_scalar;
         auto chain_kernel =
+            lean_chain  ? k_ffd_chain<false, false, true, true> :
             table_chain ? (grows ? (ps ? k_ffd_chain<true, true, true> : k_ffd_chain<true, false, true>)
                                  : (ps ? k_ffd_chain<false, true, true> : k_ffd_chain<false, false, true>))
                         : (grows ? (ps ? k_ffd_chain<true, true, false> : k_ffd_chain<true, false, false>)
@@ -4225,7 +4327,8 @@ int plan_run(ca_estimate_plan* p, const ca_limiter* lim, int32_t* last_index, ca
                                gm, grows ? p->d_slab.as<unsigned char>() : nullptr,
                                grows ? p->d_slab_off.as<int64_t>() : nullptr, grows ? p->d_gkcap.as<int32_t>() : nullptr,
                                decoupled ? 1 : 0, p->h_out.as<ChainOut>(), p->h_qc.as<int32_t>(),
-                               p->d_rstart.as<int32_t>(), p->d_rsp.as<StreamPod>(), p->s->n_cls, (int32_t)tab_off);
+                               p->d_rstart.as<int32_t>(), p->d_rsp.as<StreamPod>(), p->s->n_cls, (int32_t)tab_off,
+                               p->d_rdiv.as<double>());
             CA_HIP_CHECK(hipGetLastError());
             return CA_OK;
         };
@@ -4645,9 +4748,10 @@ int ca_estimate_plan_stats(const ca_estimate_plan* p, int32_t* rounds, float* ch
 
 int ca_estimate_plan_timings(const ca_estimate_plan* p, float* out, int32_t cap) {
     if (!p || (cap > 0 && !out)) return CA_EINVAL;
-    const int32_t n = 13;
+    const int32_t n = 14;
     for (int32_t i = 0; i < 7 && i < cap; i++) out[i] = p->t_ms[i];
     if (cap > 12) out[12] = p->opt_lists_ms;
+    if (cap > 13) out[13] = (float)p->ran_lean_chain;
     if (cap > 7) out[7] = (float)p->pub_state;
     if (cap > 8) out[8] = (float)p->ran_decoupled;
     if (cap > 9) out[9] = (float)p->ran_table_chain;

@@ -394,6 +394,7 @@ struct ca_podset {
     std::vector<int64_t> h_req;        // per pod: request cpu, memory (compact copies for plan creation)
     std::vector<uint8_t> h_pflags;     // per pod: 1 host ports, 2 extended-resource requests
     bool any_ports = false, any_scalar = false;
+    bool req_below_2p53 = true;        // every pod's cpu, memory and ephemeral request: exact in float64
     std::vector<int32_t> h_cls;        // host copies: class per pod, {cpu, memory} per class
     std::vector<int64_t> h_cls_sc;
     // every class's pods carry identical records apart from their controller

@@ -1496,6 +1496,7 @@ int ca_podset_create(ca_mirror* m, const ca_pod_table* t, ca_podset** out) {
         s->any_refs |= ps.aff_term_count > 0 || ((ps.flags & CA_POD_PREFILTER_NAMES) && ps.prefilter_count > 0);
         s->h_req[2 * (size_t)i] = ps.req_milli_cpu;
         s->h_req[2 * (size_t)i + 1] = ps.req_memory;
+        if (std::max(ps.req_milli_cpu, std::max(ps.req_memory, ps.req_ephemeral)) >= (1ll << 53)) s->req_below_2p53 = false;
         const uint32_t f = pod_dev_flags(ps);
         const uint8_t b = (uint8_t)(((f & PF_PORTS) ? 1 : 0) | ((f & PF_SCALAR_REQ) ? 2 : 0));
         s->h_pflags[i] = b;

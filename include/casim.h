@@ -522,8 +522,11 @@ int ca_estimate_plan_stats(const ca_estimate_plan* p, int32_t* rounds, float* ch
  * several workgroups of a second launch (CASIM_SORT_FAN=0: never), every other sort is one
  * part, so [11] == [10] when nothing fanned; [12] not of the last run but of the plan's
  * creation: the device time of the kernel that built the lists from the option matrix
- * (ca_estimate_plan_create_options), 0 for a plan created from host lists.  Writes
- * min(cap, 13) values; returns 13. */
+ * (ca_estimate_plan_create_options), 0 for a plan created from host lists; [13] 1 if the
+ * run-table chains of the last run were the lean instantiation (rows in LDS, no ports or
+ * extended resources, no node ordinals wanted, groups of at most 2^20 pods, every template
+ * free value and request below 2^53; CASIM_LEAN_CHAIN=0: never), else 0.  Writes
+ * min(cap, 14) values; returns 14. */
 int ca_estimate_plan_timings(const ca_estimate_plan* p, float* out, int32_t cap);
 /* Record the per-phase timing events of later runs (on: default) or not: 8 event records
  * per run on the host's launch path; with them off, ca_estimate_plan_timings[0..5] and the
