@@ -751,6 +751,29 @@ class Mirror:
                                  tried.value, hok[: a.n])
 
     def filter_stats(self) -> dict:
+        """What the last filter_out_schedulable / try_schedule_pods call did (a call with an
+        empty order leaves the earlier values).  `path`: "bitmap" (k_fb_walk) or "window"
+        (k_filter_out).  `shapes` (live request shapes plus one row for all dead ones),
+        `static_classes` and `static_in_lds` describe the bitmap walk: the first two are 0 on
+        the window kernel, which leaves `static_in_lds` as it was.  `phases` is the number of 64-pod batches begun.  Three keys count
+        different things on the two paths:
+
+        =============  ====================================  =====================================
+        key            bitmap walk                           window sequencer
+        =============  ====================================  =====================================
+        block_steps    mixed-run attempts (every time two    block-wide steps of any kind (mark,
+                       or more eligible pods are tried       next phase, ring scan, window load)
+                       together, placed or not)
+        ring_scans     pods those mixed runs placed          block-wide ring scans behind the
+                                                             512-row window
+        windows        steps of the one-by-one path (a       window loads after the first one (a
+                       hint check, a single-shape run, a     ring-scan placement or the cursor
+                       marked or PreFilter-failed pod)       running off the window)
+        =============  ====================================  =====================================
+
+        So one mixed run that places 30 pods reports (1, 30, 0) on the bitmap walk, a pure
+        single-shape run reports ring_scans == 0, and on the window kernel a ring of at most
+        512 nodes reports ring_scans == windows == 0."""
         out = (C.c_float * 16)()
         self.lib.ca_filter_stats(self.h, out, 16)
         return {"kernel_ms": out[0], "total_ms": out[1], "phases": int(out[2]), "block_steps": int(out[3]),
