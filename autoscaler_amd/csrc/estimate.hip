@@ -46,6 +46,7 @@
 #include "mirror.h"
 #include "device_filters.h"
 #include "pdqsort.h"
+#include "sort_reuse_host.h"
 
 #include <cstring>
 #include <algorithm>
@@ -1750,7 +1751,7 @@ __global__ void __launch_bounds__(256) k_publish(const GroupMeta* __restrict__ g
                                                 const int2* __restrict__ prog, int32_t pch,
                                                 T* pub,              // pub may alias sched_dev (device results)
                                                 uint64_t start_ticks, const int32_t* ids_ready, int32_t ids_epoch,
-                                                int32_t* __restrict__ hflags) {
+                                                int32_t* __restrict__ hflags, int32_t ids_final) {
     // ids_ready != null (decoupled Go order): the stream's pod ids in spod
     // come from a sort that runs beside the chains — the fan record of the group whose sort
     // wrote them (the group's own, or the representative of its sort class) flags each part
@@ -1767,6 +1768,9 @@ __global__ void __launch_bounds__(256) k_publish(const GroupMeta* __restrict__ g
     // Wave 0 is the block's controller (the other waves sleep at the barrier): it claims the
     // ticket, waits for its push, finds its positions and polls the sort's fan record — 40
     // words, one load — until the parts it needs are up.
+    // ids_final: the ids were sorted by an earlier run of the plan (or at its creation) and the
+    // host has seen that sort finished — no ticket looks up its positions or loads a fan record.
+    const bool wait_ids = ids_ready && !ids_final;
     __shared__ int32_t s_seg0;
     __shared__ int64_t s_tk;
     __shared__ Seg s_segs[64];
@@ -1816,7 +1820,7 @@ __global__ void __launch_bounds__(256) k_publish(const GroupMeta* __restrict__ g
                         const int32_t nseg = nsw & INT32_MAX;
                         const Seg* gs = segs + groups[g0].off;
                         seg0 = seg_lower(gs, nseg, a, false, lane);
-                        if (ids_ready && nsw >= 0) {
+                        if (wait_ids && nsw >= 0) {
                             if (end <= a) {
                                 s0 = s1 = 0;                         // the -1 tail alone: no ids
                             } else {
@@ -1829,7 +1833,7 @@ __global__ void __launch_bounds__(256) k_publish(const GroupMeta* __restrict__ g
                             }
                         }
                     }
-                    if (ids_ready && s0 < s1) {
+                    if (wait_ids && s0 < s1) {
                         const int32_t* fr = ids_ready + (size_t)groups[g0].ids_grp * pdq::FAN_STRIDE;
                         bool bounds = false;
                         uint32_t need = 0;
@@ -2969,6 +2973,17 @@ struct ca_estimate_plan {
     int32_t* cls_cnt() const { return d_item_cls.as<int32_t>() + total; }
     float opt_lists_ms = 0.f;      // option form: device time of k_option_lists at creation (0 otherwise)
     int32_t ids_epoch = 0;
+    // The Go-order ids belong to the plan: `ids` records the epoch and the
+    // settings d_spod_go / d_ids_ready were last sorted under, and a decoupled run whose
+    // settings match launches no sort.  Every run clears ids.valid on entry and only a
+    // decoupled run that returns CA_OK sets it again, so an error, the coupled Go sort and
+    // the radix / merge paths (which share d_pdq_e / d_pdq_scr / d_pdq_stack with the sort)
+    // all leave it invalid.  ids_sorts / ids_fan: what that sort launched (timings [10], [11]).
+    // ids_done: the host has seen the sort finished (ev_ids), so every flag is up.
+    casim::GoSortRecord ids;
+    int32_t ids_sorts = 0, ids_fan = 0;
+    bool ids_done = false;
+    int32_t ran_reused = 0;        // last run launched no Go-order sort
     // shared sorts (sort_classes): the number of sort classes — when below G their
     // representatives, in group order, follow the G records of d_meta as k_pdq_sort's group
     // map — and the number of sorts the last run launched
@@ -3517,6 +3532,7 @@ int lists_from_options(ca_estimate_plan* p, const ca_podset* s, const OptionSrc&
 // lists or from the option matrix), then the common tail: demand order, sort sharing,
 // buffers, fan map and uploads.  opt != NULL: group_off was derived from the matrix, pod_idx
 // is NULL and the lists are built on the device (k_option_lists).
+int plan_queue_first_sort(ca_estimate_plan* p);      // (below, with the run's sort helpers)
 int plan_prepare(ca_estimate_plan* p, ca_mirror* m, const ca_podset* s, const int32_t* group_off,
                  const int32_t* pod_idx, const OptionSrc* opt, const ca_template* templates, int32_t G) {
     p->m = m; p->s = s; p->G = G;
@@ -3658,6 +3674,8 @@ int plan_prepare(ca_estimate_plan* p, ca_mirror* m, const ca_podset* s, const in
         if ((rc = p->d_ids_ready.reserve(sizeof(int32_t) * fan_words)) != CA_OK) return rc;
         CA_HIP_CHECK(hipMemset(p->d_ids_ready.ptr, 0, sizeof(int32_t) * fan_words));   // epoch 0: none
         p->ids_epoch = 0;
+        // (test hook: the first sorts' epochs cross the wrap at INT32_MAX)
+        if (test_hook_env("CASIM_IDS_EPOCH_NEAR_WRAP")) p->ids_epoch = INT32_MAX - 1;
         // Defaults from profiles/sort_fan_ab.txt; knobs are read here, once
         fan_knobs(&p->fan_parts, &p->fan_min, &p->fan_steps);
         std::vector<int32_t> fan_map;
@@ -3738,7 +3756,12 @@ int plan_prepare(ca_estimate_plan* p, ca_mirror* m, const ca_podset* s, const in
     CA_HIP_CHECK(hipStreamSynchronize(st));
     if (opt && p->total > 0 && p->phase_events)
         CA_HIP_CHECK(hipEventElapsedTime(&p->opt_lists_ms, p->ev[ca_estimate_plan::EV_START], p->ev[ca_estimate_plan::EV_SCORE]));
-    return CA_OK;
+    // (the option form's inputs go back to the allocation cache before the sort is queued: a
+    // release synchronises the device and would wait for it)
+    for (DevBuf* b : {&d_eg_off, &d_eg_pod, &d_ok, &d_chunk_pre}) b->release();
+    // the Go-order ids are plan state: sorted here once, behind the lists (host lists or
+    // k_option_lists), and again only by a run whose settings differ
+    return plan_queue_first_sort(p);
 }
 
 // how long a publisher waits for the first chain of its batch to start (100 MHz ticks):
@@ -3813,6 +3836,90 @@ int launch_pdq_sort(ca_estimate_plan* p, hipStream_t ss, const int32_t* gm, int3
     return CA_OK;
 }
 
+// The decoupled path's Go-order sort: the class ranks inside the sort kernel when its LDS has
+// room for the scratch (*NP: the padded class count), else k_class_rank ahead of it
+bool go_sort_fold(const ca_estimate_plan* p, int32_t* NP) {
+    const int32_t U = p->s->n_cls;
+    int32_t np2 = 1;
+    while (np2 < U) np2 <<= 1;
+    *NP = np2;
+    const size_t npad = ((size_t)std::min(p->max_count, PDQ_LDS_N) + 63) & ~(size_t)63;
+    return 16 * (size_t)np2 <= 3 * npad && 2 * (size_t)U <= npad / 8 && !knob_env("CASIM_NO_RANK_FOLD");
+}
+
+// the settings a decoupled run sorts under (sort_reuse_host.h); the fan settings and the sort
+// classes are fixed at creation, the rank fold and the tie order are read per run
+GoSortKey go_sort_key(const ca_estimate_plan* p, bool decoupled, bool fold) {
+    GoSortKey k;
+    k.fan_parts = p->fan_parts; k.fan_min = p->fan_min; k.fan_steps = p->fan_steps;
+    k.n_sorts = p->n_sorts;
+    k.decoupled = decoupled ? 1 : 0;
+    k.fold = fold ? 1 : 0;
+    k.fanned = p->fan_parts > 0 && p->n_fan > 0 ? 1 : 0;
+    k.go_order = go_sort_order() ? 1 : 0;
+    return k;
+}
+
+// a new epoch for the sort about to be queued on st3 (wrapped: start over from a clean table)
+int go_sort_new_epoch(ca_estimate_plan* p) {
+    bool wrapped = false;
+    const int32_t next = go_sort_next_epoch(p->ids_epoch, &wrapped);
+    if (wrapped)
+        CA_HIP_CHECK(hipMemsetAsync(p->d_ids_ready.ptr, 0, sizeof(int32_t) * (size_t)pdq::FAN_STRIDE * (size_t)p->G, p->st3));
+    p->ids_epoch = next;
+    p->ids_done = false;
+    return CA_OK;
+}
+
+// Go's sort.Slice permutation of every sort class and its pod ids, on st3 under p->ids_epoch:
+// one workgroup per sort class (its representative group); the other members' consumers read
+// the representative's slice of d_spod_go and its ready flag (GroupMeta::ids_off / ids_grp)
+int queue_go_sort(ca_estimate_plan* p, bool fold, int32_t NP) {
+    const int32_t G = p->G, U = p->s->n_cls;
+    const int32_t ns = p->n_sorts;
+    const int32_t* smap = ns < G ? reinterpret_cast<const int32_t*>(p->d_meta.as<GroupMeta>() + G) : nullptr;
+    p->ran_sorts = ns;
+    if (!fold) {
+        hipLaunchKernelGGL(k_class_rank, dim3(ns), dim3(1024), 0, p->st3, p->d_meta.as<GroupMeta>(),
+                           p->d_tmpl.as<ca_template>(), p->s->d_cls_sc.as<int64_t>(), U, NP,
+                           p->d_crank2.as<int32_t>(), smap);
+        CA_HIP_CHECK(hipGetLastError());
+    }
+    return launch_pdq_sort(p, p->st3, smap, ns, p->d_crank2.as<int32_t>(), U, nullptr, 0,
+                           p->d_sortC.as<uint32_t>(), p->d_spod_go.as<int32_t>(),
+                           p->d_ids_ready.as<int32_t>(), p->ids_epoch, fold ? NP : 0);
+}
+
+// CASIM_SORT_REUSE=0 (read per run): every decoupled run sorts again (tests, A/B)
+bool sort_reuse_on() {
+    const char* e = knob_env("CASIM_SORT_REUSE");
+    return !(e && atoi(e) == 0);
+}
+
+// Plan creation (after the lists, classes and templates are on the device and m->stream is
+// drained): the sort a default run would launch, queued on st3 so that the first run behaves
+// like every later one.  Nothing waits for it here; a run that finds it still in flight has
+// its publisher wait part by part, and the other consumers wait for ev_ids.  An asynchronous
+// error surfaces at that run's hipEventQuery(ev_ids).
+int plan_queue_first_sort(ca_estimate_plan* p) {
+    const bool decoupled = go_sort_order() && p->decouple_ok && p->total > 0 &&
+                           !(knob_env("CASIM_GO_DECOUPLE") && atoi(knob_env("CASIM_GO_DECOUPLE")) == 0);
+    if (!decoupled || !sort_reuse_on()) return CA_OK;
+    int32_t NP = 1;
+    const bool fold = go_sort_fold(p, &NP);
+    int rc;
+    if ((rc = go_sort_new_epoch(p)) != CA_OK) return rc;
+    p->ran_fan = 0;
+    if ((rc = queue_go_sort(p, fold, NP)) != CA_OK) return rc;
+    CA_HIP_CHECK(hipEventRecord(p->ev_ids, p->st3));
+    p->ids.valid = true;
+    p->ids.epoch = p->ids_epoch;
+    p->ids.key = go_sort_key(p, true, fold);
+    p->ids_sorts = p->ran_sorts;
+    p->ids_fan = p->ran_fan;
+    return CA_OK;
+}
+
 int32_t pub_blocks(bool decoupled, bool table_chain) {
     const char* e = knob_env("CASIM_PUB_BLOCKS");
     // scripts/pub_sweep.sh on C2: stable order 32 x 4096-output chunks; decoupled Go order
@@ -3822,7 +3929,10 @@ int32_t pub_blocks(bool decoupled, bool table_chain) {
     // scripts/gpu_pubsweep2.sh); with round 6's chains and sort, 64 x 16384 (A/Bs of variant
     // builds: profiles/r06_pub_chunk_ab.txt, r06_pub_blocks_ab.txt); with the run-table chain
     // the publisher's tail behind the sort ends the step, not the chains: 128 blocks
-    // (profiles/table_chain_ab.txt: 0.4396 against 0.4423 ms for 64, 0.4411 for 256)
+    // (profiles/table_chain_ab.txt: 0.4396 against 0.4423 ms for 64, 0.4411 for 256); with the
+    // sort out of the step (the plan's stored ids) 32 blocks read 0.008-0.011 ms less in every
+    // round of three comparisons, under three times the 128-block rounds' own range: 128 stays
+    // (profiles/sort_reuse_ab.txt)
 #ifndef CASIM_PUB_BLOCKS_DECOUPLED
 #define CASIM_PUB_BLOCKS_DECOUPLED 64
 #endif
@@ -3952,43 +4062,55 @@ int plan_run(ca_estimate_plan* p, const ca_limiter* lim, int32_t* last_index, ca
     // bounds when the publisher can start and ends well before them), else before anything
     // else (sort_first, below).
     // (the run's epoch is set before anything is queued: every consumer launched below reads it)
-    if (decoupled) {
-        if (p->ids_epoch == INT32_MAX) {                  // (wrapped: start over from a clean table)
-            CA_HIP_CHECK(hipMemsetAsync(p->d_ids_ready.ptr, 0, sizeof(int32_t) * (size_t)pdq::FAN_STRIDE * (size_t)G, p->st3));
-            p->ids_epoch = 0;
+    //
+    // The ids are plan state: a decoupled run whose settings match the record of the stored
+    // ids (ca_estimate_plan::ids) keeps their epoch and launches no sort — its consumers find
+    // every flag up, or wait as usual if the sort queued at creation is still in flight.
+    // Every other decoupled run sorts under a new epoch.  The record is cleared here and set
+    // again where the run returns CA_OK, so a run that fails, and every run that is not
+    // decoupled (the coupled Go sort and the merge path write d_pdq_e / d_pdq_scr /
+    // d_pdq_stack), leaves it invalid.
+    int32_t sort_NP = 1;
+    const bool sort_fold = decoupled && go_sort_fold(p, &sort_NP);
+    const GoSortKey sort_key = go_sort_key(p, decoupled, sort_fold);
+    const bool reuse_ids = go_sort_reusable(p->ids, sort_key, sort_reuse_on());
+    p->ids.valid = false;
+    p->ran_reused = reuse_ids ? 1 : 0;
+    // ids_final: the stored ids' sort is known finished — nothing waits for ids in this run
+    bool ids_final = false;
+    if (reuse_ids || (p->decouple_ok && !decoupled)) {
+        if (!p->ids_done) {
+            if (reuse_ids) {
+                const hipError_t q = hipEventQuery(p->ev_ids);
+                if (q == hipSuccess) p->ids_done = true;
+                else if (q == hipErrorNotReady) (void)hipGetLastError();
+                else CA_HIP_CHECK(q);                     // (an error of the sort queued at creation)
+            } else {
+                // a sort may still be running on st3 with the scratch this run's own sort uses
+                CA_HIP_CHECK(hipStreamSynchronize(p->st3));
+                p->ids_done = true;
+            }
         }
-        p->ids_epoch++;
+        ids_final = reuse_ids && p->ids_done;
+    }
+    if (reuse_ids) {
+        p->ran_sorts = p->ids_sorts;
+        p->ran_fan = p->ids_fan;
+        st_mark(0);
+    } else if (decoupled) {
+        int rce;
+        if ((rce = go_sort_new_epoch(p)) != CA_OK) return rce;
     }
     auto launch_go_sort = [&]() -> int {
-        const int32_t U = p->s->n_cls;
-        int32_t NP = 1;
-        while (NP < U) NP <<= 1;
-        // the class ranks inside the sort kernel when its LDS has room for the scratch
-        const size_t npad = ((size_t)std::min(p->max_count, PDQ_LDS_N) + 63) & ~(size_t)63;
-        const bool fold = 16 * (size_t)NP <= 3 * npad && 2 * (size_t)U <= npad / 8 && !knob_env("CASIM_NO_RANK_FOLD");
-        // one workgroup per sort class (its representative group); the other members' consumers
-        // read the representative's slice of d_spod_go and its ready flag (GroupMeta::ids_off / ids_grp)
-        const int32_t ns = p->n_sorts;
-        const int32_t* smap = ns < G ? reinterpret_cast<const int32_t*>(p->d_meta.as<GroupMeta>() + G) : nullptr;
-        p->ran_sorts = ns;
-        if (!fold) {
-            hipLaunchKernelGGL(k_class_rank, dim3(ns), dim3(1024), 0, p->st3, p->d_meta.as<GroupMeta>(),
-                               p->d_tmpl.as<ca_template>(), p->s->d_cls_sc.as<int64_t>(), U, NP,
-                               p->d_crank2.as<int32_t>(), smap);
-            CA_HIP_CHECK(hipGetLastError());
-        }
         int rc0;
-        if ((rc0 = launch_pdq_sort(p, p->st3, smap, ns, p->d_crank2.as<int32_t>(), U, nullptr, 0,
-                                   p->d_sortC.as<uint32_t>(), p->d_spod_go.as<int32_t>(),
-                                   p->d_ids_ready.as<int32_t>(), p->ids_epoch, fold ? NP : 0)) != CA_OK)
-            return rc0;
+        if ((rc0 = queue_go_sort(p, sort_fold, sort_NP)) != CA_OK) return rc0;
         st_mark(0);
         return CA_OK;
     };
-    bool go_sort_queued = !decoupled;
+    bool go_sort_queued = !decoupled || reuse_ids;
     // (ev_ids is recorded on st3 once the heavy chains are queued: the host's launches ahead
-    // of them pace the step's start)
-    bool ids_recorded = !decoupled;
+    // of them pace the step's start; a run that reuses the ids keeps the sort's own record)
+    bool ids_recorded = !decoupled || reuse_ids;
     auto record_ids = [&]() -> int {
         if (!ids_recorded) { CA_HIP_CHECK(hipEventRecord(p->ev_ids, p->st3)); ids_recorded = true; }
         return CA_OK;
@@ -4092,6 +4214,9 @@ int plan_run(ca_estimate_plan* p, const ca_limiter* lim, int32_t* last_index, ca
         gmapB = gmapA + p->n_heavy;
     }
     const int32_t nA = split ? p->n_heavy : G, nB = split ? G - p->n_heavy : 0;
+    // The usual decoupled run uses the plan's stored ids and has no sort to queue: the heavy
+    // run table and chains are the first launches of the step, nothing is queued on st3 and
+    // no consumer waits for ev_ids.  What follows orders a run that does sort.
     // With the run-table chain the sort is launched first and the heavy run table right behind
     // it.  Since a segment ticket waits only for the sort parts it reads and k_run_table takes
     // its counts from the plan, the publisher ends ~5 us after the heavy chain and the step
@@ -4286,14 +4411,15 @@ int plan_run(ca_estimate_plan* p, const ca_limiter* lim, int32_t* last_index, ca
                                    ids_src, p->d_sched_pod.as<int32_t>(), p->d_tickets.as<int64_t>(),
                                    p->d_qctl.as<int32_t>(), round_tickets, p->nsub, p->d_prog.as<int2>(), p->pch,
                                    reinterpret_cast<uint16_t*>(publish), pub_start_ticks(),
-                                   decoupled ? p->d_ids_ready.as<int32_t>() : nullptr, p->ids_epoch, p->h_qc.as<int32_t>());
+                                   decoupled ? p->d_ids_ready.as<int32_t>() : nullptr, p->ids_epoch, p->h_qc.as<int32_t>(),
+                                   ids_final ? 1 : 0);
             else
                 hipLaunchKernelGGL(k_publish<int32_t>, dim3(std::min(round_tickets, pub_blocks(decoupled, table_chain))), dim3(256), 0, ps,
                                    p->d_meta.as<GroupMeta>(), p->d_out.as<ChainOut>(), p->d_seg.as<Seg>(),
                                    ids_src, p->d_sched_pod.as<int32_t>(), p->d_tickets.as<int64_t>(),
                                    p->d_qctl.as<int32_t>(), round_tickets, p->nsub, p->d_prog.as<int2>(), p->pch,
                                    publish, pub_start_ticks(), decoupled ? p->d_ids_ready.as<int32_t>() : nullptr, p->ids_epoch,
-                                   p->h_qc.as<int32_t>());
+                                   p->h_qc.as<int32_t>(), ids_final ? 1 : 0);
             CA_HIP_CHECK(hipGetLastError());
             return CA_OK;
         };
@@ -4443,7 +4569,7 @@ int plan_run(ca_estimate_plan* p, const ca_limiter* lim, int32_t* last_index, ca
     // k_copy_segments the run placements (or the publisher, into the caller's buffer)
     if (decoupled && !publish && p->total > 0) {
         // once, after the last round: stream positions -> Go-order ids
-        CA_HIP_CHECK(hipStreamWaitEvent(st, p->ev_ids, 0));
+        if (!ids_final) CA_HIP_CHECK(hipStreamWaitEvent(st, p->ev_ids, 0));
         hipLaunchKernelGGL(k_copy_segments, dim3((p->max_count + CPY_PER_BLOCK - 1) / CPY_PER_BLOCK, G), dim3(256), 0,
                            st, p->d_meta.as<GroupMeta>(), p->d_out.as<ChainOut>(), p->d_seg.as<Seg>(),
                            ids_src, p->d_sched_pod.as<int32_t>(),
@@ -4461,7 +4587,7 @@ int plan_run(ca_estimate_plan* p, const ca_limiter* lim, int32_t* last_index, ca
         if (pub_gave_up || qc[2] != 0 || qc[3] != 0) {
             p->pub_state = 2;
             set_last_error("estimate publisher missed a ticket; results copied instead");
-            if (decoupled) CA_HIP_CHECK(hipStreamWaitEvent(st, p->ev_ids, 0));
+            if (decoupled && !ids_final) CA_HIP_CHECK(hipStreamWaitEvent(st, p->ev_ids, 0));
             hipLaunchKernelGGL(k_copy_segments, dim3((p->max_count + CPY_PER_BLOCK - 1) / CPY_PER_BLOCK, G), dim3(256), 0,
                                st, p->d_meta.as<GroupMeta>(), p->d_out.as<ChainOut>(), p->d_seg.as<Seg>(),
                                ids_src, p->d_sched_pod.as<int32_t>(), nullptr, decoupled ? 1 : 0);
@@ -4529,7 +4655,7 @@ int plan_run(ca_estimate_plan* p, const ca_limiter* lim, int32_t* last_index, ca
     }
     p->stats.rounds = rounds;
     p->stats.kernel_ms = chain_ms;
-    p->stats.sort_ms = sort_ms;
+    p->stats.sort_ms = reuse_ids ? 0.f : sort_ms;      // (a run that launched no Go-order sort)
     p->stats.total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_start).count();
     p->t_ms[6] = p->stats.total_ms;
     if (step_timing) {
@@ -4557,6 +4683,15 @@ int plan_run(ca_estimate_plan* p, const ca_limiter* lim, int32_t* last_index, ca
     // (a publisher that ran to its end wrote the caller's buffer only: d_sched_pod then holds
     // stream positions or single placements alone)
     p->lists_final = !publish || p->pub_state == 2;
+    if (decoupled) {
+        // the ids in d_spod_go / d_ids_ready are this run's (sorted or kept): the next run
+        // with the same settings uses them
+        p->ids.valid = true;
+        p->ids.epoch = p->ids_epoch;
+        p->ids.key = sort_key;
+        p->ids_sorts = p->ran_sorts;
+        p->ids_fan = p->ran_fan;
+    }
     return CA_OK;
 }
 
@@ -4748,8 +4883,9 @@ int ca_estimate_plan_stats(const ca_estimate_plan* p, int32_t* rounds, float* ch
 
 int ca_estimate_plan_timings(const ca_estimate_plan* p, float* out, int32_t cap) {
     if (!p || (cap > 0 && !out)) return CA_EINVAL;
-    const int32_t n = 14;
+    const int32_t n = 15;
     for (int32_t i = 0; i < 7 && i < cap; i++) out[i] = p->t_ms[i];
+    if (cap > 14) out[14] = (float)p->ran_reused;
     if (cap > 12) out[12] = p->opt_lists_ms;
     if (cap > 13) out[13] = (float)p->ran_lean_chain;
     if (cap > 7) out[7] = (float)p->pub_state;
@@ -4757,11 +4893,14 @@ int ca_estimate_plan_timings(const ca_estimate_plan* p, float* out, int32_t cap)
     if (cap > 9) out[9] = (float)p->ran_table_chain;
     if (cap > 10) out[10] = (float)p->ran_sorts;
     if (cap > 11) {
-        // the parts are decided on the device: read the fan records of the run (every run is
-        // synchronised before it returns)
+        // the parts are decided on the device: read the fan records of the sort whose ids the
+        // run used (a sort queued at creation, or one whose last parts no ticket read, may
+        // still be running: st3 is drained first)
         int32_t parts = p->ran_sorts;
         if (p->ran_decoupled && p->ran_fan) {
             const int32_t G = p->G;
+            CA_HIP_CHECK(hipSetDevice(p->m->device));
+            CA_HIP_CHECK(hipStreamSynchronize(p->st3));
             std::vector<int32_t> rec((size_t)pdq::FAN_STRIDE * (size_t)std::max(G, 1));
             CA_HIP_CHECK(hipMemcpy(rec.data(), p->d_ids_ready.ptr, sizeof(int32_t) * rec.size(), hipMemcpyDeviceToHost));
             parts = 0;

@@ -1337,15 +1337,15 @@ class EstimatePlan:
         self.lib.ca_estimate_plan_stats(self.h, C.byref(r), C.byref(a), C.byref(b), C.byref(c))
         sens, succ = C.c_int32(0), C.c_int32(0)
         self.lib.ca_estimate_plan_chain_info(self.h, C.byref(sens), C.byref(succ))
-        t = (C.c_float * 14)()
-        self.lib.ca_estimate_plan_timings(self.h, t, 14)
+        t = (C.c_float * 15)()
+        self.lib.ca_estimate_plan_timings(self.h, t, 15)
         names = ("score_ms", "merge_ms", "emit_ms", "chain_ms", "compact_ms", "d2h_ms", "host_ms")
         return {"rounds": r.value, "chain_ms": a.value, "sort_ms": b.value, "total_ms": c.value,
                 "lin_sensitive": sens.value, "had_success": succ.value,
                 "phases": {k: float(v) for k, v in zip(names, t)},
                 "results_path": ("copied", "published", "publisher_gave_up")[int(t[7])],
                 "decoupled": bool(t[8]), "table_chain": bool(t[9]), "lean_chain": bool(t[13]), "sorts": int(t[10]),
-                "sort_parts": int(t[11]), "option_lists_ms": float(t[12])}
+                "sort_parts": int(t[11]), "sort_reused": bool(t[14]), "option_lists_ms": float(t[12])}
 
     def set_phase_timing(self, on: bool) -> None:
         """Per-phase timing events on later runs (on by default; off keeps them off the

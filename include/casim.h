@@ -515,18 +515,23 @@ int ca_estimate_plan_stats(const ca_estimate_plan* p, int32_t* rounds, float* ch
  * two classes of a group with equal scores), else 0; [9] 1 if the decoupled chains walked
  * the per-class run table in LDS (no stream emission: run batching on, and the table of
  * the podset's score classes fits the chain's LDS beside its rows), else 0 — the chains
- * read the emitted stream; [10] the Go-order sorts the run launched: groups with equal pod
- * lists whose templates rank the podset's score classes alike share one on the decoupled
- * path (CASIM_SORT_SHARE=0: one per group), otherwise the number of groups; [11] the
- * parts those sorts' ids were finished and flagged in: a long list's sort fans out over
+ * read the emitted stream; [10] the Go-order sorts that produced the ids the run used (its
+ * own, or on the decoupled path those of the plan's creation or of an earlier run, see [14]):
+ * groups with equal pod lists whose templates rank the podset's score classes alike share
+ * one on the decoupled path (CASIM_SORT_SHARE=0: one per group), otherwise the number of
+ * groups; [11] the parts those sorts' ids were finished and flagged in: a long list's sort fans out over
  * several workgroups of a second launch (CASIM_SORT_FAN=0: never), every other sort is one
  * part, so [11] == [10] when nothing fanned; [12] not of the last run but of the plan's
  * creation: the device time of the kernel that built the lists from the option matrix
  * (ca_estimate_plan_create_options), 0 for a plan created from host lists; [13] 1 if the
  * run-table chains of the last run were the lean instantiation (rows in LDS, no ports or
  * extended resources, no node ordinals wanted, groups of at most 2^20 pods, every template
- * free value and request below 2^53; CASIM_LEAN_CHAIN=0: never), else 0.  Writes
- * min(cap, 14) values; returns 14. */
+ * free value and request below 2^53; CASIM_LEAN_CHAIN=0: never), else 0; [14] 1 if the run
+ * launched no Go-order sort: the ids of the decoupled path belong to the plan — they are
+ * sorted once, queued when the plan is created, and a run sorts again only when its settings
+ * differ from theirs, after a run that failed or was not decoupled, or with
+ * CASIM_SORT_REUSE=0 (every run sorts); ca_estimate_plan_stats' sort_ms is 0 for such a
+ * run.  Writes min(cap, 15) values; returns 15. */
 int ca_estimate_plan_timings(const ca_estimate_plan* p, float* out, int32_t cap);
 /* Record the per-phase timing events of later runs (on: default) or not: 8 event records
  * per run on the host's launch path; with them off, ca_estimate_plan_timings[0..5] and the
