@@ -47,6 +47,7 @@
 #include "device_filters.h"
 #include "pdqsort.h"
 #include "sort_reuse_host.h"
+#include "chain_owner_host.h"
 
 #include <cstring>
 #include <algorithm>
@@ -714,6 +715,7 @@ __global__ void __launch_bounds__(256) k_cls_hist(const GroupMeta* __restrict__ 
 // for free == 0) and fmin(., cap) gives cap — a zero request passes whenever free >= 0.
 __device__ inline double run_req(int64_t req) { return (double)req; }
 __device__ inline double run_rcp(int64_t req) { return req > 0 ? 1.0 / (double)req : __builtin_inf(); }
+constexpr int RDIV_N = 7;      // doubles per rank in k_run_table's rdiv: 3 requests, 3 reciprocals, fresh-copy count
 
 __device__ inline int32_t run_rank(const int32_t* __restrict__ st, int32_t U, int32_t i) {
     int32_t lo = 0, hi = U;                  // the last r with st[r] <= i (st[U] is never read)
@@ -739,7 +741,9 @@ __global__ void __launch_bounds__(1024) k_run_table(const GroupMeta* __restrict_
     // lin != null: round 1 without k_round_init — the group's lastIndex input, need flag and
     // unsupported flag are set here (stored, not or-ed)
     // rdiv != null: rdiv[g][r][0..6) the rank's requests and their reciprocals in float64
-    // (run_div's values, one thread per class here instead of once per run on the chain)
+    // (run_div's values, one thread per class here instead of once per run on the chain), and
+    // rdiv[g][r][6] the copies of the class's pod on a fresh template copy, capped at the
+    // group's pod count (the lean chain's closed-form opening takes min(., pods left in the run))
     __shared__ int32_t cnt[CLS_MAX];
     __shared__ uint32_t s_unsup;
     __shared__ int32_t rc[CLS_MAX];
@@ -820,12 +824,13 @@ __global__ void __launch_bounds__(1024) k_run_table(const GroupMeta* __restrict_
         sp.flags = sf | (batchable(p, sf) ? SF_BATCH : 0u);
         rsp[(size_t)gi * U + cr[c]] = sp;
         if (rdiv) {
-            double* d = rdiv + ((size_t)gi * U + cr[c]) * 6;
+            double* d = rdiv + ((size_t)gi * U + cr[c]) * RDIV_N;
             const int64_t req[3] = {p.cpu, p.mem, p.eph};
             for (int i = 0; i < 3; i++) {
                 d[i] = run_req(req[i]);
                 d[3 + i] = run_rcp(req[i]);
             }
+            d[6] = (double)co_fresh_copies(gm.tcpu, gm.tmem, gm.teph, gm.tpods, d, d + 3, (sf & SF_ZERO) != 0, gm.count);
         }
         unsup |= sf & SF_UNSUP;
     }
@@ -1308,11 +1313,12 @@ __global__ void __launch_bounds__(256) k_emit_bucket(const GroupMeta* __restrict
 
 // 4. the First-Fit-Decreasing chain -------------------------------------------
 #ifdef CASIM_PROF   // section cycle counters of k_ffd_chain (profiling build only)
-constexpr int NPROF = 23;   // + [12] loop top (window moves, head reads), [13] epilogue, [14] before the loop
+constexpr int NPROF = 24;   // + [12] loop top (window moves, head reads), [13] epilogue, [14] before the loop
 // [15..16] blocks over all row passes, of the wave that sent most to the quotients: rows read,
 // admitted to the float64 quotients ([17] that wave); [18..19] the row pass split: rows (with
 // the wave reductions the compiler schedules ahead of the clock), cross-wave exchange;
-// [20..22] an opening: the template's copy count, row writes and barrier, evals and segment
+// [20..22] an opening: the template's copy count, row writes (the generic chain: and their
+// barrier), evals and segment; [23] workgroup barriers executed in the loop
 __device__ unsigned long long g_chain_prof[1024][NPROF];
 #define PROF_T(v) const uint64_t v = clock64()
 #define PROF_ADD(i, t) prof[i] += clock64() - (t)
@@ -1345,9 +1351,13 @@ __device__ inline int32_t mbcnt(uint64_t m) {
 
 // The chain workgroup: CW wavefronts, one per SIMD of the CU.  Every wave runs the same
 // sequential control flow on the same (uniform) state; the per-row loops over the
-// group's new nodes are split across the waves (row j -> thread j mod CT), so the
-// row work of a run — copy counts, revolution lists, row updates, opened rows — runs
-// on all four SIMDs.  Cross-wave reductions go through LDS, double-buffered by a parity
+// group's new nodes are split across the waves in 64-row blocks (row j -> lane j mod 64
+// of one wave: the generic chain deals the blocks out in contiguous ranges from the
+// current row count, wave_rows; the lean chain gives block b to wave b mod CW for the
+// whole kernel, chain_owner_host.h), so the row work of a run — copy counts, level
+// counts, row updates, opened rows — runs on all four SIMDs; the placement list of a
+// call that wants node ordinals is dealt thread by thread (rotated rank rr -> thread
+// rr mod CT).  Cross-wave reductions go through LDS, double-buffered by a parity
 // bit so that one barrier per reduction suffices (a wave cannot reach the next use of
 // a buffer before every wave has read it: that needs the barrier in between).
 // Barrier that orders LDS only.  __syncthreads() is also a workgroup fence for global
@@ -1446,6 +1456,31 @@ __device__ inline void wave_rows(int32_t k, int wv, int32_t& lo, int32_t& hi) {
     const int32_t cpw = (((k + 63) >> 6) + CW - 1) / CW;      // 64-row chunks per wave
     lo = min(k, wv * cpw * 64);
     hi = min(k, lo + cpw * 64);
+}
+// The lean chain's cross-wave exchange (32-bit: a run's copy sum is only used as min(S, rem)
+// with rem <= 2^20, so each wave's part saturates at rem) and its per-block counts of
+// qualifying rows (block b in bc[.][b]; at most 64 blocks), double-buffered like ChainRed.
+struct LeanX {
+    int32_t v[2][CW][RED_N + 3];      // (32 B per wave)
+    int32_t bc[2][64];
+};
+// inclusive prefix sum across the 64 lanes (DPP row shifts, then row broadcasts 15 / 31);
+// every lane active
+__device__ inline int32_t lane_incl_scan(int32_t v) {
+    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false);     // row_shr:1
+    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false);     // row_shr:2
+    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, false);     // row_shr:4
+    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false);     // row_shr:8
+    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);     // row_bcast:15 -> rows 1, 3
+    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);     // row_bcast:31 -> rows 2, 3
+    return v;
+}
+// LDS written by one lane of a wave and read by another lane of the same wave: the hardware
+// runs a wave's LDS operations in order; this keeps the compiler from moving them across.
+__device__ inline void wave_lds_order() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
 }
 // Evals of opening n_open template copies for the rest of a run (closed form of the
 // per-node sum: node i's opening pod fails FitsAnyNode over the k0+i rows before it
@@ -1551,13 +1586,7 @@ __device__ inline RunDiv run_div(int64_t pcpu, int64_t pmem, int64_t peph, int64
 // fma(-q, req, free) = free - q*req is an integer below 2^53 in magnitude, so it is
 // computed exactly and one step each way makes q exact (no 64-bit integer multiply).
 __device__ inline int32_t dim_copies_f64(int64_t free_, double rd, double rcpd, int32_t cap) {
-    const double fd = (double)(free_ < 0 ? 0 : free_);
-    const double cp = (double)cap;
-    double q = fmin(floor(fd * rcpd), cp);              // NaN (0 * inf) -> cap
-    const double t = fma(-q, rd, fd);
-    q += ((t >= rd) & (q < cp)) ? 1.0 : 0.0;
-    q -= (t < 0.0) ? 1.0 : 0.0;
-    return free_ < 0 ? 0 : (int32_t)q;
+    return co_dim_copies_f64(free_, rd, rcpd, cap);     // (chain_owner_host.h: checked on the host)
 }
 // SREQ: the zero-request tests read the scalar integer requests (the lean chain's float64
 // values come from LDS in vector registers; the test is the same one)
@@ -1981,8 +2010,11 @@ __global__ void __launch_bounds__(256) k_publish(const GroupMeta* __restrict__ g
 // fact).  Such a call never takes the integer rec_copies path, the rem > 2^20 path or the
 // placement list, so they are not instantiated, and a run's float64 requests and reciprocals
 // come from the table (rdiv, k_run_table) instead of three divisions and the conversions at
-// its entry.  The loop is otherwise the generic one; every other call runs the generic
-// instantiations.
+// its entry, as does the copy count of its pod on a fresh template copy.  Its runs have a body
+// of their own: every 64-row block belongs to one wave for the whole kernel, so a run costs
+// one barrier (the exchange) where the generic body needs two (the invariants: at its top).
+// Every other call runs the generic instantiations, the in-tree reference of the lean one
+// (CASIM_LEAN_CHAIN=0).
 template <bool GROWS, bool PS, bool TB, bool LEAN = false>
 __global__ void __launch_bounds__(CT) k_ffd_chain(
     const GroupMeta* __restrict__ groups, const StreamPod* __restrict__ stream, const uint64_t* __restrict__ heads,
@@ -2023,6 +2055,7 @@ __global__ void __launch_bounds__(CT) k_ffd_chain(
     const int wv = tid >> 6;          // wave of the workgroup
     const bool w0 = wv == 0;          // the wave that stores single-pod results
     __shared__ ChainRed cred;
+    __shared__ LeanX lx;              // (the lean chain's exchange; unused and dropped elsewhere)
     int par = 0;
     const GroupMeta gm = groups[g];
     const int32_t lin = lin_arr[g];
@@ -2052,6 +2085,11 @@ __global__ void __launch_bounds__(CT) k_ffd_chain(
     int32_t k = 0;              // new nodes so far
     int32_t granted = 0;        // limiter.nodes
     int32_t last_node = -1;     // lastNodeName
+    // LEAN: R[last_node].used in a uniform register (known at every opening, derived from the
+    // copy counts at every placement), the kind of the previous step (1 a run, 2 one pod: a
+    // barrier separates the two), and the parities of the exchange buffers and of CAPA / ALIVE
+    bool l_used = false;
+    int prev_step = 0, lpar = 0, lcap = 0;
     int32_t L = lin;            // the checker's lastIndex
     int32_t nsched = 0;
     uint64_t evals = 0;
@@ -2092,25 +2130,33 @@ __global__ void __launch_bounds__(CT) k_ffd_chain(
     // run's end, the rank of the run after) in registers, read from LDS when the run before
     // started, so taking a run waits for nothing.
     // LEAN: TDIV[r] behind TREC — the rank's three requests and their reciprocals in float64
-    // (48 B), kept in registers one run ahead like the record (t_ndiv).
+    // (48 B), kept in registers one run ahead like the record (t_ndiv), and TRCT[r] behind TST:
+    // the copies of the rank's pod on a fresh template copy (k_run_table's rdiv[.][6]; t_nct).
     struct RankDiv { double v[6]; };
     StreamPod* const TREC = reinterpret_cast<StreamPod*>(smem_raw + tab_off);
     RankDiv* const TDIV = reinterpret_cast<RankDiv*>(TREC + (TB ? U : 0));
     int2* const TRUN = reinterpret_cast<int2*>(TDIV + (LEAN ? U : 0));
     int32_t* const TST = reinterpret_cast<int32_t*>(TRUN + (TB ? U + 1 : 0));
+    int32_t* const TRCT = TST + (TB ? U + 1 : 0);
     int32_t t_next = 0, t_end = 0, n_runs = 0;     // the next run of the list; the current run's end
     StreamPod t_nrec = {};
     RankDiv t_ndiv = {}, t_div = {};
+    int32_t t_nct = 0, t_ct = 0;
     int2 t_npair = make_int2(0, 0);
     if (TB) {
         const StreamPod* rp = rsp + (size_t)g * U;
-        const RankDiv* dp = LEAN ? reinterpret_cast<const RankDiv*>(rdiv) + (size_t)g * U : nullptr;
+        const double* dp = LEAN ? rdiv + (size_t)g * U * RDIV_N : nullptr;
         for (int32_t r = tid; r < U; r += CT) {
             // (the first CT ranks' starts were requested at the kernel's entry)
             const int32_t a = r < CT ? t_a0 : t_rs[r], b = r < CT ? t_b0 : t_rs[r + 1];
             TST[r] = a;
             if (b > a) TREC[r] = rp[r];        // (an absent rank's record was never written)
-            if (LEAN && b > a) TDIV[r] = dp[r];
+            if (LEAN && b > a) {
+                RankDiv dr;
+                for (int i = 0; i < 6; i++) dr.v[i] = dp[(size_t)r * RDIV_N + i];
+                TDIV[r] = dr;
+                TRCT[r] = (int32_t)dp[(size_t)r * RDIV_N + 6];
+            }
         }
         if (tid == 0) TST[U] = P;
         cbar<GROWS>();
@@ -2134,7 +2180,7 @@ __global__ void __launch_bounds__(CT) k_ffd_chain(
         if (tid == 0) TRUN[n_runs] = make_int2(0, P);
         cbar<GROWS>();
         t_nrec = TREC[TRUN[0].x];
-        if (LEAN) t_ndiv = TDIV[TRUN[0].x];
+        if (LEAN) { t_ndiv = TDIV[TRUN[0].x]; t_nct = TRCT[TRUN[0].x]; }
         t_npair = TRUN[min(1, n_runs)];
     }
 
@@ -2151,6 +2197,7 @@ __global__ void __launch_bounds__(CT) k_ffd_chain(
             SC[(size_t)tid * kcap + nn] = wsub(tp.node.alloc_scalar[tid], tp.used_scalar[tid]);
         k++;
         last_node = nn;
+        l_used = false;
         return nn;
     };
     auto note_success = [&]() {
@@ -2218,7 +2265,7 @@ __global__ void __launch_bounds__(CT) k_ffd_chain(
             cur.flags |= SF_HEAD;           // a batchable run is entered at its head only
             t_end = rl32(t_npair.y, 0);
             t_next++;
-            if (LEAN) { t_div = t_ndiv; t_ndiv = TDIV[t_npair.x]; }
+            if (LEAN) { t_div = t_ndiv; t_ndiv = TDIV[t_npair.x]; t_ct = t_nct; t_nct = TRCT[t_npair.x]; }
             t_nrec = TREC[t_npair.x];       // the run after: in flight behind this run's LDS work
             t_npair = TRUN[min(t_next + 1, n_runs)];
         }
@@ -2254,20 +2301,363 @@ __global__ void __launch_bounds__(CT) k_ffd_chain(
                 pf_hw = pf_hc + lane < nhc ? hm[pf_hc + lane] : 0ull;
             }
             PROF_ADD(0, t_re);
-            if (e - pos >= 2) {
+            if constexpr (LEAN) if (e - pos >= 2) {
+                // ---- the lean run: wave-owned rows, one barrier per row pass ----
+                // 64-row block b belongs to wave co_owner(b) for the whole kernel, whatever k
+                // is, and the owner does all row work of its blocks: the row pass, the update
+                // after the pick, the single-row update, the rows of an opening.  A wave thus
+                // reads back only rows it wrote itself (a wave's LDS operations are ordered),
+                // and a run needs no barrier beyond its exchange.  What holds:
+                //  * Order-dependent results come from per-block counts (lx.bc, lane = block
+                //    after the exchange): the t-th qualifying row in row order is one prefix
+                //    over the lanes and one ballot on that block's counts.  Sums, minima and
+                //    the last row with room stay per-wave values (lx.v, 32-bit).
+                //  * The copy counts alternate between CAPA and ALIVE with each row pass, the
+                //    exchange records between the halves of lx with each exchange: a wave that
+                //    is ahead writes the next pass's values while another still picks from
+                //    this one's.  Between two writes of a shared word by different passes lies
+                //    an exchange barrier that every reader of the first value has passed.
+                //  * A pick reads counts only in a block whose published count is positive (the
+                //    owner wrote every row of it in this pass); CAPA[last_node] likewise.
+                //  * R[last_node].used is the uniform l_used, never read from the row here.
+                //  * No wave reads a row another wave wrote without a barrier between: the
+                //    exhausted path (R[last_node] after an opening), the empty-node path
+                //    (open_node: thread 0 writes) and the per-pod path (rows, SUM: entered and
+                //    left through a barrier, prev_step) keep barriers of their own, and the
+                //    epilogue's count of used rows follows one.  All of these are cold.
+                //  * Every barrier is in workgroup-uniform control flow (the conditions are the
+                //    exchanged values and the run's uniform state).  A run without exchange has
+                //    no barrier at all (k == 0: straight to the opening), so the buffer
+                //    parities follow the exchanges and row passes, not the runs.
+                PROF_INC(7);
+                PROF_T(t_pro);
+                if (prev_step == 2) { PROF_INC(23); cbar<false>(); }      // the per-pod path's row and SUM writes
+                prev_step = 1;
+                const int32_t RN = e - pos;
+                const uint64_t kev = (sf & SF_EVAL) ? 1u : 0u;
+                RunDiv dv;      // from the table: no division and no conversion at a run's entry
+                for (int i = 0; i < 3; i++) { dv.reqd[i] = t_div.v[i]; dv.rcpd[i] = t_div.v[3 + i]; }
+                dv.f64 = true;
+                int32_t done = 0;
+                bool exhausted = false;          // every row but last_node has no room left
+                PROF_ADD(8, t_pro);
+                while (done < RN) {
+                    const int32_t rem = RN - done;
+                    const int32_t len = n_base + k;
+                    int32_t placed = 0;
+                    if ((sf & SF_FA_OK) && k > 0) {
+                        int32_t s0 = L;
+                        if (s0 >= len) s0 = (int32_t)((uint32_t)s0 % (uint32_t)len);
+                        const int32_t j0 = s0 > n_base ? s0 - n_base : 0;   // first new node visited
+                        const int32_t nbw = co_wave_blocks(k, wv, CW);      // this wave's blocks
+                        int32_t one = -1, n_one = 0, nalive = 0, S = 0;
+                        int32_t lv_cmin = 0;      // revolution 1: fewest copies among rows with room
+                        int32_t lv_s = 0;         // ... and how many of them lie before j0
+                        int32_t bc1 = 0;          // lane = block: its rows with room
+                        uint64_t adm_w = 0;       // bit i: the wave's i-th block has copy counts
+                        int32_t* CAP = CAPA;      // this pass's copy counts
+                        if (exhausted) {
+                            PROF_T(t_ex);
+                            PROF_ADDN(23, 2);
+                            cbar<false>();    // the row's last write (an opening, open_node) is visible
+                            const NodeRec rl_ = R[last_node];
+                            const int32_t c = rec_copies_run<true>(rl_, dv, zero, rem, pcpu, pmem, peph);
+                            cbar<false>();    // every wave has read the row before its owner changes it
+                            if (c > 0) { one = last_node; n_one = c; nalive = 1; }
+                            PROF_ADD(10, t_ex);
+                        } else {
+                            PROF_T(t_ca);
+                            CAP = lcap ? ALIVE : CAPA;
+                            lcap ^= 1;
+                            wave_lds_order();     // rows this wave's other lanes opened or updated
+                            // copies per row of the wave's blocks (two in flight), only where some
+                            // row fits (rec_fits: compares only); for revolution 1 (rows with
+                            // room): count per block, last such row, fewest copies, count below j0
+                            int32_t s32 = 0, cm = INT32_MAX;          // copies (<= 2^24 per lane), fewest
+                            int32_t na_w = 0, lt_w = 0, a1_w = -1;    // wave-uniform
+                            int32_t cnt_l = 0;                        // lane i: rows with room in the wave's i-th block
+                            auto acc = [&](int32_t i, int32_t b, int32_t c, bool in) -> int32_t {   // row 64 b + lane
+                                if (in) CAP[(b << 6) + lane] = c;
+                                const bool room = in && c > 0;
+                                cm = room ? min(cm, c) : cm;
+                                const uint64_t m = __ballot(room);
+                                const int32_t pc = __builtin_popcountll(m);
+                                na_w += pc;
+                                lt_w += __builtin_popcountll(m & lanes_below(j0 - (b << 6)));
+                                if (m) a1_w = (b << 6) + hibit(m);
+                                cnt_l = lane == i ? pc : cnt_l;
+                                return in ? c : 0;
+                            };
+                            for (int32_t i = 0; i < nbw; i += 2) {
+                                const int32_t b0 = co_wave_block(wv, i, CW), b1 = co_wave_block(wv, i + 1, CW);
+                                const int32_t ja = (b0 << 6) + lane, jb = (b1 << 6) + lane;
+                                const bool in0 = ja < k, in1 = i + 1 < nbw && jb < k;
+                                // (a lane past the rows reads the wave's own first row of the pair)
+                                const NodeRec r0 = R[in0 ? ja : b0 << 6], r1 = R[in1 ? jb : b0 << 6];
+                                const uint64_t f0 = __ballot(in0 && rec_fits(r0, pcpu, pmem, peph, zero));
+                                const uint64_t f1 = __ballot(in1 && rec_fits(r1, pcpu, pmem, peph, zero));
+                                PROF_ADDN(15, 1 + (i + 1 < nbw));
+                                PROF_ADDN(16, (f0 != 0) + (f1 != 0));
+                                if (f0) {
+                                    adm_w |= 1ull << i;
+                                    s32 += acc(i, b0, rec_copies_run(r0, dv, zero, rem, pcpu, pmem, peph), in0);
+                                }
+                                if (f1) {
+                                    adm_w |= 1ull << (i + 1);
+                                    s32 += acc(i + 1, b1, rec_copies_run(r1, dv, zero, rem, pcpu, pmem, peph), in1);
+                                }
+                            }
+                            PROF_ADD(18, t_ca);
+                            PROF_T(t_wr);
+                            // S (each part saturated at rem), rows with room, last such row,
+                            // fewest copies, rows < j0; and the per-block counts
+                            const int32_t xs = min(__ockl_wfred_add_i32(s32), rem), xm = wave_min32(cm);
+                            if (lane == 0) {
+                                int32_t* v = lx.v[lpar][wv];
+                                v[0] = xs; v[1] = na_w; v[2] = a1_w; v[3] = xm; v[4] = lt_w;
+                            }
+                            if (lane < nbw) lx.bc[lpar][co_wave_block(wv, lane, CW)] = cnt_l;
+                            PROF_INC(23);
+                            cbar<false>();            // + this pass's copy counts visible
+                            int32_t a1 = -1;
+                            lv_cmin = INT32_MAX;
+                            for (int w = 0; w < CW; w++) {
+                                const int32_t* v = lx.v[lpar][w];
+                                S += v[0]; nalive += v[1]; a1 = max(a1, v[2]); lv_cmin = min(lv_cmin, v[3]); lv_s += v[4];
+                            }
+                            bc1 = lane < co_blocks(k) ? lx.bc[lpar][lane] : 0;
+                            lpar ^= 1;
+                            PROF_ADD(19, t_wr);
+                            if (nalive == 1) { one = a1; n_one = min(S, rem); }
+                            PROF_ADD(1, t_ca);
+                        }
+                        if (nalive == 1) {
+                            // every remaining copy goes to the one row with room; its owner writes it
+                            int32_t rho = one - j0;
+                            if (rho < 0) rho += k;
+                            evals += (uint64_t)rho + 1 + (uint64_t)(n_one - 1) * (uint64_t)k;
+                            if (wv == co_owner(one >> 6, CW) && lane == 0) {
+                                NodeRec r = R[one];
+                                r.cpu -= (int64_t)n_one * pcpu;
+                                r.mem -= (int64_t)n_one * pmem;
+                                r.eph -= (int64_t)n_one * peph;
+                                r.pods -= n_one;
+                                r.used = 1;
+                                R[one] = r;
+                            }
+                            L = n_base + one + 1;
+                            if (L >= len) L -= len;
+                            note_success();
+                            placed = n_one;
+                            l_used |= one == last_node;
+                        } else if (nalive > 1) {
+                            const int32_t n = min(S, rem);
+                            PROF_T(t_rv);
+                            // A level (revolutions r..cmin, rows with >= r copies) is a count, and
+                            // only the last placement's row matters: the m-th row of its revolution
+                            // in rotated order, i.e. the t-th qualifying row in row order, found by
+                            // every wave from the blocks' counts and one ballot: no barrier.
+                            int32_t got = 0, r = 1, last = -1;
+                            int32_t lv_na = nalive, lv_bc = bc1;
+                            for (;;) {
+                                const int64_t avail = (int64_t)(lv_cmin - r + 1) * (int64_t)lv_na;
+                                if ((int64_t)got + avail >= n) {
+                                    const int32_t m0 = n - got;
+                                    r += (m0 - 1) / lv_na;
+                                    const int32_t m = (m0 - 1) % lv_na + 1;        // rank in rotated order
+                                    const int32_t t = co_row_rank(m, lv_na, lv_s); // rank in row order (1-based)
+                                    const int32_t incl = lane_incl_scan(lv_bc);
+                                    const int32_t b = __builtin_ctzll(__ballot(co_block_holds(incl, lv_bc, t)));
+                                    const int32_t tb = co_rank_in_block(rl32(incl, b), rl32(lv_bc, b), t);
+                                    const int32_t j = (b << 6) + lane;
+                                    const uint64_t bm = __ballot(j < k && CAP[j] >= r);
+                                    const bool hit = ((bm >> lane) & 1ull) && mbcnt(bm) == tb - 1;
+                                    last = (b << 6) + __builtin_ctzll(__ballot(hit));
+                                    got = n;
+                                    PROF_INC(6);
+                                    break;
+                                }
+                                got += (int32_t)avail;
+                                r = lv_cmin + 1;
+                                // the next level: rows with at least r copies (one more exchange)
+                                int32_t cnt_w = 0, lt2 = 0, cm2 = INT32_MAX, cnt_l = 0;
+                                for (int32_t i = 0; i < nbw; i++) {
+                                    if (!((adm_w >> i) & 1ull)) continue;
+                                    const int32_t b = co_wave_block(wv, i, CW);
+                                    const int32_t j = (b << 6) + lane;
+                                    const int32_t c = j < k ? CAP[j] : 0;
+                                    const bool q = c >= r;
+                                    cm2 = q ? min(cm2, c) : cm2;
+                                    const uint64_t m = __ballot(q);
+                                    const int32_t pc = __builtin_popcountll(m);
+                                    cnt_w += pc;
+                                    lt2 += __builtin_popcountll(m & lanes_below(j0 - (b << 6)));
+                                    cnt_l = lane == i ? pc : cnt_l;
+                                }
+                                const int32_t xm = wave_min32(cm2);
+                                if (lane == 0) {
+                                    int32_t* v = lx.v[lpar][wv];
+                                    v[1] = cnt_w; v[3] = xm; v[4] = lt2;
+                                }
+                                if (lane < nbw) lx.bc[lpar][co_wave_block(wv, lane, CW)] = cnt_l;
+                                PROF_INC(23);
+                                cbar<false>();
+                                lv_na = 0; lv_cmin = INT32_MAX; lv_s = 0;
+                                for (int w = 0; w < CW; w++) {
+                                    const int32_t* v = lx.v[lpar][w];
+                                    lv_na += v[1]; lv_cmin = min(lv_cmin, v[3]); lv_s += v[4];
+                                }
+                                lv_bc = lane < co_blocks(k) ? lx.bc[lpar][lane] : 0;
+                                lpar ^= 1;
+                                PROF_INC(6);
+                            }
+                            PROF_ADD(2, t_rv);
+                            PROF_T(t_up);
+                            int32_t rl = last - j0;
+                            if (rl < 0) rl += k;
+                            evals += (uint64_t)(r - 1) * (uint64_t)k + (uint64_t)rl + 1;
+                            // the wave's own rows, blocks with counts only (others: no room)
+                            for (int32_t i = 0; i < nbw; i++) {
+                                if (!((adm_w >> i) & 1ull)) continue;
+                                const int32_t j = (co_wave_block(wv, i, CW) << 6) + lane;
+                                const int32_t c = j < k ? CAP[j] : 0;
+                                int32_t rj = j - j0;
+                                if (rj < 0) rj += k;
+                                const int32_t nj = min(c, r - 1) + ((c >= r && rj <= rl) ? 1 : 0);
+                                if (nj > 0) {
+                                    NodeRec q = R[j];
+                                    q.cpu -= (int64_t)nj * pcpu;
+                                    q.mem -= (int64_t)nj * pmem;
+                                    q.eph -= (int64_t)nj * peph;
+                                    q.pods -= nj;
+                                    q.used = 1;
+                                    R[j] = q;
+                                }
+                            }
+                            PROF_ADD(3, t_up);
+                            if (last_node >= 0 && !l_used) {      // (the update's nj of last_node)
+                                const int32_t c = rl32(bc1, last_node >> 6) > 0 ? CAP[last_node] : 0;
+                                int32_t rj = last_node - j0;
+                                if (rj < 0) rj += k;
+                                l_used = min(c, r - 1) + ((c >= r && rj <= rl) ? 1 : 0) > 0;
+                            }
+                            L = n_base + last + 1;
+                            if (L >= len) L -= len;
+                            note_success();
+                            placed = n;
+                        }
+                    }
+                    PROF_T(t_pb);
+                    // (no barrier here: the rows updated above are read by their owners only)
+                    if (tid == 0 && placed > 0) gseg[nseg] = Seg{nsched, pos + done, placed, 0};
+                    if (placed > 0) note_segment(nsched, pos + done);
+                    nseg += placed > 0 ? 1 : 0;
+                    nsched += placed;
+                    done += placed;
+                    progress();
+                    if (done == RN) break;
+                    exhausted = true;
+                    // the next pod of the run fails FitsAnyNode: every new node visited
+                    evals += kev * (uint64_t)k;
+                    if (max_nodes > 0 && granted >= max_nodes) { stop = true; break; }
+                    granted++;
+                    PROF_ADD(9, t_pb);
+                    if (last_node >= 0 && !l_used) {
+                        // :114-116 — and every later pod of the run repeats this pod's fate
+                        done++;
+                        const int32_t q = RN - done;
+                        if (max_nodes > 0 && q > max_nodes - granted) {
+                            const int32_t allowed = max_nodes - granted;
+                            evals += (uint64_t)(allowed + 1) * kev * (uint64_t)k;
+                            granted = max_nodes;
+                            stop = true;
+                            break;
+                        }
+                        evals += (uint64_t)q * kev * (uint64_t)k;
+                        granted += q;
+                        done = RN;
+                        break;
+                    }
+                    if (k >= kcap) { res.status = CA_ECAPACITY; stop = true; break; }
+                    const int32_t rem2 = RN - done;
+                    if (!((sf & SF_CP_OK) && rec_fits(trec, pcpu, pmem, peph, zero))) {
+                        // CheckPredicates on the new node fails: it stays empty and the next pod
+                        // of the run takes the empty-node skip above.  Thread 0 writes the row
+                        // and its block's summary, whoever owns them: between barriers.
+                        PROF_ADDN(23, 2);
+                        cbar<false>();
+                        open_node();
+                        if (sf & SF_CP_EVAL) evals++;
+                        done++;
+                        cbar<false>();
+                        continue;
+                    }
+                    // Every row is full for this pod, so each remaining pod group opens a fresh
+                    // template copy (the closed form of the generic body below); ct, the copies
+                    // on a fresh copy, is the table's constant clipped to the pods left.
+                    PROF_T(t_op);
+                    const int32_t ct = !(sf & SF_FA_OK) ? 1 : min(t_ct, rem2);
+                    PROF_ADD(20, t_op);
+                    PROF_T(t_ow);
+                    int32_t n_open = (rem2 + ct - 1) / ct;
+                    if (max_nodes > 0) n_open = min(n_open, 1 + (max_nodes - granted));
+                    n_open = min(n_open, kcap - k);
+                    const int32_t k0 = k;
+                    const int32_t placed2 = min(rem2, n_open * ct);
+                    const int32_t len0 = n_base + k0 + 1;
+                    int32_t s00 = L;
+                    if (s00 >= len0) s00 = (int32_t)((uint32_t)s00 % (uint32_t)len0);
+                    const int32_t j00 = s00 > n_base ? s00 - n_base : 0;
+                    // each wave writes the opened rows of its blocks, and those blocks' summaries
+                    for (int32_t b = co_first_block(k0 >> 6, wv, CW); (b << 6) < k0 + n_open; b += CW) {
+                        int32_t lo, hi;
+                        co_open_rows(k0, n_open, b, lo, hi);
+                        const int32_t j = (b << 6) + lane;
+                        if (j >= lo && j < hi) {
+                            const int32_t i = j - k0;
+                            const int32_t pi = (i == n_open - 1) ? placed2 - i * ct : ct;
+                            NodeRec r = trec;
+                            r.cpu -= (int64_t)pi * pcpu;
+                            r.mem -= (int64_t)pi * pmem;
+                            r.eph -= (int64_t)pi * peph;
+                            r.pods -= pi;
+                            r.used = 1;
+                            R[j] = r;
+                        }
+                        if (lane == 0) SUM[b] = trec;
+                    }
+                    PROF_ADD(21, t_ow);
+                    PROF_T(t_oe);
+                    evals += open_evals(n_open, ct, placed2, k0, j00, kev, (sf & SF_CP_EVAL) != 0);
+                    if (tid == 0 && placed2 > 0) gseg[nseg] = Seg{nsched, pos + done, placed2, 0};
+                    if (placed2 > 0) note_segment(nsched, pos + done);
+                    nseg += placed2 > 0 ? 1 : 0;
+                    if (ct >= 2 && placed2 >= 2) {
+                        if (!first_success) { first_success = true; sensitive = k0 + 1 >= 2; }
+                        L = 0;       // n_base + (last row) + 1 == len
+                    }
+                    k = k0 + n_open;
+                    last_node = k - 1;
+                    l_used = true;       // every opened row holds at least one pod of the run
+                    granted += n_open - 1;
+                    nsched += placed2;
+                    done += placed2;
+                    progress();
+                    PROF_ADD(22, t_oe);
+                    PROF_ADD(4, t_op);
+                }
+                pos = e;
+                PROF_ADD(11, t_run);
+                continue;
+            }
+            if (!LEAN && e - pos >= 2) {     // (the generic run: two barriers, rows dealt out from k)
                 PROF_INC(7);
                 PROF_T(t_pro);
                 const int32_t RN = e - pos;
                 const uint64_t kev = (sf & SF_EVAL) ? 1u : 0u;
                 // the pod's reciprocals, once per run (copy counts of every row, the last
                 // row and the template: fast path while the cap is <= 2^20)
-                RunDiv dv;
-                if (LEAN) {     // from the table: no division and no conversion at a run's entry
-                    for (int i = 0; i < 3; i++) { dv.reqd[i] = t_div.v[i]; dv.rcpd[i] = t_div.v[3 + i]; }
-                    dv.f64 = true;
-                } else {
-                    dv = run_div(pcpu, pmem, peph, max(trec.cpu, max(trec.mem, trec.eph)));
-                }
+                const RunDiv dv = run_div(pcpu, pmem, peph, max(trec.cpu, max(trec.mem, trec.eph)));
                 int32_t done = 0;
                 bool exhausted = false;          // every row but last_node has no room left
                 PROF_ADD(8, t_pro);
@@ -2293,9 +2683,9 @@ __global__ void __launch_bounds__(CT) k_ffd_chain(
                         if (exhausted) {
                             PROF_T(t_ex);
                             const NodeRec rl_ = R[last_node];
-                            const int32_t c = LEAN ? rec_copies_run<true>(rl_, dv, zero, rem, pcpu, pmem, peph)
-                                              : rem <= (1 << 20) ? rec_copies_run(rl_, dv, zero, rem, pcpu, pmem, peph)
-                                                                 : rec_copies(rl_, pcpu, pmem, peph, zero, rem);
+                            const int32_t c = rem <= (1 << 20) ? rec_copies_run(rl_, dv, zero, rem, pcpu, pmem, peph)
+                                                               : rec_copies(rl_, pcpu, pmem, peph, zero, rem);
+                            PROF_INC(23);
                             cbar<GROWS>();    // every wave has read the row before it changes
                             if (c > 0) { one = last_node; n_one = c; nalive = 1; }
                             PROF_ADD(10, t_ex);
@@ -2320,7 +2710,7 @@ __global__ void __launch_bounds__(CT) k_ffd_chain(
                                 if (m) a1_w = b + hibit(m);
                                 return in ? c : 0;
                             };
-                            const bool fast = LEAN || rem <= (1 << 20);
+                            const bool fast = rem <= (1 << 20);
                             if (fast) {
                                 // Block skip: a row has room for a copy iff the pod fits it
                                 // (rec_fits: compares only), so the float64 copy counts run
@@ -2364,6 +2754,7 @@ __global__ void __launch_bounds__(CT) k_ffd_chain(
                             x[0] = fast ? (int64_t)__ockl_wfred_add_i32(s32) : wave_sum64(s64);
                             x[1] = na_w; x[2] = a1_w; x[3] = wave_min32(cm); x[4] = lt_w;
                             constexpr int OPS[RED_N] = {R_SUM, R_SUM, R_MAX, R_MIN, R_SUM};
+                            PROF_INC(23);
                             blk_xchg5<GROWS>(cred, par, wv, lane, x, OPS);     // + CAPA visible
                             PROF_ADD(19, t_wr);
                             S = x[0];
@@ -2457,6 +2848,7 @@ __global__ void __launch_bounds__(CT) k_ffd_chain(
                                 }
                                 int64_t y[RED_N] = {0, cnt_w, 0, wave_min32(cm2), lt2};   // -, count, -, min, count < j0
                                 constexpr int OPS2[RED_N] = {R_SUM, R_SUM, R_SUM, R_MIN, R_SUM};
+                                PROF_INC(23);
                                 blk_xchg5<GROWS>(cred, par, wv, lane, y, OPS2);
                                 lv_buf = par ^ 1;
                                 lv_na = (int32_t)y[1];
@@ -2576,7 +2968,7 @@ __global__ void __launch_bounds__(CT) k_ffd_chain(
                     nsched += placed;
                     done += placed;
                     progress();
-                    if (done == RN) { cbar<GROWS>(); break; }
+                    if (done == RN) { PROF_INC(23); cbar<GROWS>(); break; }
                     exhausted = true;
                     // the next pod of the run fails FitsAnyNode: every new node visited
                     evals += kev * (uint64_t)k;
@@ -2597,6 +2989,7 @@ __global__ void __launch_bounds__(CT) k_ffd_chain(
                         evals += (uint64_t)q * kev * (uint64_t)k;
                         granted += q;
                         done = RN;
+                        PROF_INC(23);
                         cbar<GROWS>();
                         break;
                     }
@@ -2608,6 +3001,7 @@ __global__ void __launch_bounds__(CT) k_ffd_chain(
                         open_node();
                         if (sf & SF_CP_EVAL) evals++;
                         done++;
+                        PROF_INC(23);
                         cbar<GROWS>();
                         continue;
                     }
@@ -2619,7 +3013,6 @@ __global__ void __launch_bounds__(CT) k_ffd_chain(
                     // and takes one limiter grant.  Closed form over n_open nodes.
                     PROF_T(t_op);
                     const int32_t ct = !(sf & SF_FA_OK) ? 1
-                                       : LEAN ? rec_copies_run<true>(trec, dv, zero, rem2, pcpu, pmem, peph)
                                        : rem2 <= (1 << 20) ? rec_copies_run(trec, dv, zero, rem2, pcpu, pmem, peph)
                                                            : rec_copies(trec, pcpu, pmem, peph, zero, rem2);
                     PROF_ADD(20, t_op);
@@ -2654,6 +3047,7 @@ __global__ void __launch_bounds__(CT) k_ffd_chain(
                             SC[(size_t)sc * kcap + node] = wsub(tp.node.alloc_scalar[sc], tp.used_scalar[sc]);
                         }
                     }
+                    PROF_INC(23);
                     cbar<GROWS>();                                                  // new rows visible
                     PROF_ADD(21, t_ow);
                     PROF_T(t_oe);
@@ -2693,6 +3087,10 @@ __global__ void __launch_bounds__(CT) k_ffd_chain(
         }
         pos++;
         n_single++;
+        if (LEAN) {     // the run before wrote rows and summaries with no barrier behind them
+            if (prev_step == 1) { PROF_INC(23); cbar<false>(); }
+            prev_step = 2;
+        }
 
         // ---- FitsAnyNodeMatching(newNodeNames) (binpacking_estimator.go:91-93) ----
         int32_t found = -1;
@@ -2772,8 +3170,9 @@ __global__ void __launch_bounds__(CT) k_ffd_chain(
             // PermissionToAddNode (threshold_based_limiter.go:46-56), before the empty-node skip
             if (max_nodes > 0 && granted >= max_nodes) break;
             granted++;
-            if (last_node >= 0 && !R[last_node].used) continue;               // :114-116
+            if (last_node >= 0 && !(LEAN ? l_used : R[last_node].used != 0)) continue;   // :114-116
             if (k >= kcap) { res.status = CA_ECAPACITY; break; }
+            PROF_INC(23);
             cbar<GROWS>();                    // every wave's scan is done before rows change
             const int32_t nn = open_node();
             // CheckPredicates(pod, newNode) (:132-134)
@@ -2791,9 +3190,10 @@ __global__ void __launch_bounds__(CT) k_ffd_chain(
                     ok = c == 0;
                 }
             }
-            if (!ok) { cbar<GROWS>(); continue; }
+            if (!ok) { PROF_INC(23); cbar<GROWS>(); continue; }
             found = nn;
         }
+        PROF_INC(23);
         cbar<GROWS>();                        // every wave's scan is done before R[found] changes
         // AddPod(pod, node) (:96 / :135) — NodeInfo.update on the new-node row
         if (tid == 0) {
@@ -2805,6 +3205,7 @@ __global__ void __launch_bounds__(CT) k_ffd_chain(
             r.used = 1;
             R[found] = r;
         }
+        l_used |= found == last_node;
         if (w0 && lane == sl) { out_node = found; out_idx = nsched; pend = true; }
         if (PS && (sf & SF_SCALAR)) {
             if (tid < CA_MAX_SCALAR) {
@@ -2818,6 +3219,7 @@ __global__ void __launch_bounds__(CT) k_ffd_chain(
         nsched++;
         pure_from = nsched;                   // a single placement: written by the chain itself
         progress();
+        PROF_INC(23);
         cbar<GROWS>();                        // the placement is visible to every wave
     }
     PROF_T(t_epi);
@@ -2962,7 +3364,7 @@ struct ca_estimate_plan {
     // permutation; d_ids_ready: per group, the run epoch whose ids are final there)
     DevBuf d_sortC, d_ids_ready, d_spod_go, d_crank2;
     DevBuf d_rstart, d_rsp;        // decoupled: per group, each rank's first stream position and record
-    DevBuf d_rdiv;                 // ... and its requests and their reciprocals in float64 (6 per rank: the lean chain)
+    DevBuf d_rdiv;                 // ... and its requests and their reciprocals in float64 (RDIV_N per rank: the lean chain)
     // every template's free values and every pod's requests are below 2^53: float64 copy
     // counts are exact for every run of this plan (a condition of the lean chain)
     bool f64_exact = false;
@@ -3696,7 +4098,7 @@ int plan_prepare(ca_estimate_plan* p, ca_mirror* m, const ca_podset* s, const in
             return rc;
         if ((rc = p->d_rsp.reserve(sizeof(StreamPod) * (size_t)std::max(G, 1) * (size_t)std::max(s->n_cls, 1))) != CA_OK)
             return rc;
-        if ((rc = p->d_rdiv.reserve(sizeof(double) * 6 * (size_t)std::max(G, 1) * (size_t)std::max(s->n_cls, 1))) != CA_OK)
+        if ((rc = p->d_rdiv.reserve(sizeof(double) * RDIV_N * (size_t)std::max(G, 1) * (size_t)std::max(s->n_cls, 1))) != CA_OK)
             return rc;
     }
     if (G) CA_HIP_CHECK(hipMemcpyAsync(p->d_meta.ptr, p->h_meta.data(), sizeof(GroupMeta) * G, hipMemcpyHostToDevice, st));
@@ -3942,9 +4344,10 @@ int32_t pub_blocks(bool decoupled, bool table_chain) {
 // The run-table chain's table of a podset with U score classes (k_ffd_chain<.., TB>): a
 // 32-B record and a first position per rank, and the list of (rank, first position) of
 // the ranks that start a run.
-// lean: and the rank's float64 requests and reciprocals (48 B) behind its record.
+// lean: and the rank's float64 requests and reciprocals (48 B) behind its record, and its copy
+// count on a fresh template copy (4 B).
 size_t chain_table_bytes(int32_t U, bool lean = false) {
-    return ((sizeof(StreamPod) + (lean ? 6 * sizeof(double) : 0)) * (size_t)U +
+    return ((sizeof(StreamPod) + (lean ? 6 * sizeof(double) + sizeof(int32_t) : 0)) * (size_t)U +
             (sizeof(int2) + sizeof(int32_t)) * ((size_t)U + 1) + 15) & ~(size_t)15;
 }
 // table_ranks >= 0: with the run table of that many classes behind the rows (which start
@@ -4150,7 +4553,7 @@ int plan_run(ca_estimate_plan* p, const ca_limiter* lim, int32_t* last_index, ca
                       !(knob_env("CASIM_LEAN_CHAIN") && atoi(knob_env("CASIM_LEAN_CHAIN")) == 0);
     if (lean_chain) {
         const size_t with_lean = chain_lds_bytes(kcap, false, false, p->s->n_cls, true);
-        if (with_lean + sizeof(ChainRed) > 160 * 1024) lean_chain = false;
+        if (with_lean + sizeof(ChainRed) + sizeof(LeanX) > 160 * 1024) lean_chain = false;
         else lds = with_lean;
     }
     p->ran_table_chain = table_chain ? 1 : 0;

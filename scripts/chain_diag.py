@@ -29,15 +29,21 @@ if os.environ.get("CASIM_LIB_PATH", "").endswith("libcasim_prof.so"):
     lib = native.load()
     G = len(w.templates)
     print("lean_chain", plan.stats()["lean_chain"])
-    buf = np.zeros((G, 23), np.uint64)
+    buf = np.zeros((G, 24), np.uint64)
     lib.ca_debug_chain_prof(buf.ctypes.data_as(C.POINTER(C.c_uint64)), G)
     # capa = capa_rows + capa_xchg; open = open_ct + open_rows_bar + open_evals_seg; blk_read /
     # blk_quot: blocks read and blocks sent to the quotients over all row passes by the wave
     # that sent most (blk_wave), i.e. the busiest wave
     names = ["run_end", "capa", "revol", "update", "open", "total", "n_rev", "n_runs", "prologue", "post_bar", "exhausted", "run_total", "loop_top", "epilogue", "pre_loop",
-             "blk_read", "blk_quot", "blk_wave", "capa_rows", "capa_xchg", "open_ct", "open_rows_bar", "open_evals_seg"]
+             "blk_read", "blk_quot", "blk_wave", "capa_rows", "capa_xchg", "open_ct", "open_rows_bar", "open_evals_seg",
+             "n_bar"]
     for g in order[:6]:
         print(f"g{g:3d} " + " ".join(f"{n}={int(v)}" for n, v in zip(names, buf[g])))
+    # workgroup barriers executed in the chain's loop: the lean chain needs one per run that had an
+    # exchange (rows open and FitsAnyNode possible) plus one per copy level beyond the first
+    for g in order[:6]:
+        runs, bars, levels = int(buf[g][7]), int(buf[g][23]), int(buf[g][6])
+        print(f"g{g:3d} barriers={bars} runs={runs} levels={levels} barriers/run={bars / max(runs, 1):.2f}")
 
     if hasattr(lib, "ca_debug_rt_prof"):
         rt = np.zeros((G, 3), np.uint64)
